@@ -12,6 +12,20 @@ all-gathers when N > 1.  N > 1 is weak scaling of this workload: rank r owns
 its own 162,541-user shard of one global dataset (same items); value = all
 ratings / max-over-ranks time.
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only that: it generates
+the data, builds the CSR blocks, warms up, times the K steps and prints the line
+(`value`, `ms_per_step`, the event-time roofline of the timed steps' own launches).
+`--dump-outputs DIR` also writes what the last timed step left, the user and item
+factor tables a caller of the fit receives, as DIR/user_factors.npy and
+DIR/item_factors.npy (float32; at most 64 MB in all, a fixed seeded row sample with
+its row numbers in DIR/<name>_rows.npy when the tables are larger).  Data and initial
+factors are seeded, so two builds run with the same arguments can be compared array
+for array.
+
+Everything below runs only with `--full` (`--only W` implies it): the top-10 timing,
+the training RMSE, the rescued-row count (one more iteration), the CPU baseline, the
+live counter passes and the secondary workloads.
+
 Secondary objects on the same line (the other BASELINE configs, each at full size;
 `--no-big` skips them):
   configs2: configs[2], the same ML-25M data with implicitPrefs=True, alpha 40,
@@ -165,7 +179,7 @@ def live_counters(timeout_s: int = 150) -> dict:
     import subprocess
     import tempfile
     rec = {"passes": [p for p, _ in LIVE_PASSES], "workload": "configs1",
-           "command": "bench.py --only c1 --steps 3 --warmup 1 --no-rmse"}
+           "command": "bench.py --full --only c1 --steps 3 --warmup 1 --no-rmse"}
     prof = shutil.which("rocprofv3")
     if any(k.startswith("ROCPROF") for k in os.environ):
         # this run is itself profiled (rocprofv3 ... -- python3 bench.py): its children
@@ -178,7 +192,7 @@ def live_counters(timeout_s: int = 150) -> dict:
     t0 = time.perf_counter()
     tmp = tempfile.mkdtemp(prefix="als_pmc_", dir="/tmp")
     env = dict(os.environ, TMPDIR="/tmp")
-    cmd_tail = ["--", sys.executable, os.path.join(ROOT, "bench.py"), "--only", "c1",
+    cmd_tail = ["--", sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--only", "c1",
                 "--steps", "3", "--warmup", "1", "--no-rmse", "--no-live-pmc"]
     dirs = []
     try:
@@ -646,10 +660,12 @@ def rescued_rows(core, k, reg, imp, alpha):
     return out
 
 
-def timed_fit(core, workload, k, reg, imp, alpha, steps, warmup):
+def timed_fit(core, workload, k, reg, imp, alpha, steps, warmup, full=True, keep=None):
     """warmup + `steps` timed iterations from the seeded start; per-iteration wall time
     and the event times of the primal and dual launches of each half-sweep
-    -> (ms_per_iter, roofline of the primal kernel, dual view)."""
+    -> (ms_per_iter, roofline of the primal kernel, dual view).  keep: a dict that
+    receives copies of the factor tables as the last timed step left them; full: also
+    count the rescued rows (one more, untimed, iteration)."""
     core.init_factors(k, seed=5)
     core.schedule_for(imp)  # the engine's heavy-row task length for this fit
     core.status.zero_()
@@ -663,6 +679,9 @@ def timed_fit(core, workload, k, reg, imp, alpha, steps, warmup):
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
     core.check_status()
+    if keep is not None:
+        keep["user_factors"] = core.U[:core.n_users, :k].clone()
+        keep["item_factors"] = core.V[:core.n_items, :k].clone()
     ib, ub = core.item_block, core.user_block
 
     def avg(a, b):
@@ -675,8 +694,34 @@ def timed_fit(core, workload, k, reg, imp, alpha, steps, warmup):
     roof = roofline(workload, dominant_kernel(k, imp), launches, k, imp)
     dual = None if imp else dual_view(workload, k, {"item": ib, "user": ub},
                                       {"item": avg(1, 2), "user": avg(4, 5)}, reg)
-    roof["fp64_rescued_rows_per_half_sweep"] = rescued_rows(core, k, reg, imp, alpha)
+    if full:
+        roof["fp64_rescued_rows_per_half_sweep"] = rescued_rows(core, k, reg, imp, alpha)
     return 1e3 * dt, roof, dual
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path: str, arrays: dict) -> dict:
+    """Write each [rows, k] tensor of `arrays` as path/<name>.npy (float32).  Past
+    DUMP_BUDGET_BYTES in all, every table keeps the same fraction of its rows, a sorted
+    sample drawn with a fixed seed, and path/<name>_rows.npy (float64) names the rows."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.numel() * 4 for a in arrays.values())
+    rec = {}
+    for j, (name, a) in enumerate(arrays.items()):
+        x = a.detach().to(torch.float32).cpu().numpy()
+        if total > DUMP_BUDGET_BYTES:
+            row_bytes = 4 * x.shape[1] + 8  # the row and its number
+            share = DUMP_BUDGET_BYTES * (x.size * 4 / total)
+            n = max(1, min(x.shape[0], int(0.98 * share / row_bytes)))
+            rows = np.sort(np.random.default_rng(1234 + j).choice(x.shape[0], n, replace=False))
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            x = x[rows]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(x))
+        rec[name] = {"shape": list(x.shape), "of_rows": int(a.shape[0]), "dtype": "float32"}
+    return rec
 
 
 def configs2(core, args):
@@ -759,12 +804,11 @@ def run_single(args, live=None):
     k = args.rank
     imp, alpha = args.implicit, args.alpha
     wl = "configs2" if (imp and k == 128) else "configs1"
+    keep = {} if args.dump_outputs else None
     ms_per_step, roof, dual = timed_fit(core, wl, k, args.reg, imp, alpha, args.steps,
-                                        args.warmup)
+                                        args.warmup, args.full, keep)
     value = core.nnz / (ms_per_step * 1e-3)
     ib, ub = core.item_block, core.user_block
-    # top-10 recommendations for all users (K5)
-    topk_ms = _timed_topk(core.U, core.n_users, core.V, core.n_items, k, 10)
     mode = f"implicit alpha={alpha:g}" if imp else "explicit"
     cfg_idx = 2 if (imp and k == 128) else 1
     out = {
@@ -786,24 +830,32 @@ def run_single(args, live=None):
                    "rank": k, "regParam": args.reg, "implicitPrefs": imp, "alpha": alpha,
                    "parallelism": "dp1"},
         "roofline": roof,
-        "live_counters": live,
         "dual": dual,
         "library": library_record(),
-        "topk10_recs_per_s": core.n_users / (topk_ms * 1e-3),
-        "topk10_ms": topk_ms,
-        "topk_roofline": topk_roofline("configs1", core.n_users, core.n_items, k, topk_ms, 10),
         "csr_build_ms": build_ms,
         "datagen_s": t_gen,
         "schedule": {"item": [ib.n_light, ib.n_heavy, ib.n_chunks],
                      "user": [ub.n_light, ub.n_heavy, ub.n_chunks]},
+        "full": args.full,
+        "cpu_baseline": None,
     }
+    if keep is not None:
+        out["dumped_outputs"] = dump_outputs(args.dump_outputs, keep)
+        keep.clear()
+    if not args.full:
+        print(json.dumps(out), file=OUT, flush=True)
+        return
+    out["live_counters"] = live
+    # top-10 recommendations for all users (K5)
+    topk_ms = _timed_topk(core.U, core.n_users, core.V, core.n_items, k, 10)
+    out["topk10_recs_per_s"] = core.n_users / (topk_ms * 1e-3)
+    out["topk10_ms"] = topk_ms
+    out["topk_roofline"] = topk_roofline("configs1", core.n_users, core.n_items, k, topk_ms, 10)
     if args.rmse:
         rmse, n = core.rmse(*_train_triples(core))
         out["train_rmse"] = rmse
     if args.cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(core, k, args.reg, args.cpu_budget, imp, alpha)
-    else:
-        out["cpu_baseline"] = None
     if args.big and not imp and args.config == "ml25m":
         try:
             out["configs2"] = configs2(core, args)
@@ -919,6 +971,13 @@ def run_distributed(args):
     sh.init_factors(k, seed=5)
     t_total = _timed_iterations(sh, args.reg, args.warmup, args.steps, dev)
     ex = dict(sh.exchange_stats(k), mode=sh.exchange, pipelined=sh.pipeline)
+    dumped = None
+    if args.dump_outputs:  # the replicated tables, in id order; rank 0 writes them
+        keep = {"user_factors": sh.user_factors(cache=False)[1],
+                "item_factors": sh.item_factors(cache=False)[1]}
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, keep)
+        del keep
     out = None
     if rank == 0:
         out = {
@@ -942,7 +1001,10 @@ def run_distributed(args):
             "roofline": None,
             "cpu_baseline": None,
             "library": library_record(),
+            "full": args.full,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
     del sh
     torch.cuda.empty_cache()
     if args.big:
@@ -982,6 +1044,12 @@ def main():
     ap.add_argument("--reg", type=float, default=0.1)
     ap.add_argument("--implicit", action="store_true", help="implicitPrefs=True (configs[2])")
     ap.add_argument("--alpha", type=float, default=40.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: top-10, training "
+                         "RMSE, rescued rows, CPU baseline, live counter passes and the "
+                         "configs[2]-[4] workloads (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the factor tables the last timed step left as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", dest="cpu_baseline", action="store_false")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--no-rmse", dest="rmse", action="store_false")
@@ -1003,6 +1071,15 @@ def main():
                     help="N = 1: skip the rocprofv3 child passes that measure the headline "
                          "kernel's counters in this run (the committed profile is used)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.only:  # a profiling run of one workload is never the plain run
+        args.full = True
+    if args.dump_outputs and args.only in ("c2", "c3", "c4"):
+        ap.error("--dump-outputs writes the headline workload's factors: not with --only "
+                 + args.only)
+    if not args.full:
+        args.big = args.cpu_baseline = args.rmse = args.live_pmc = False
     if args.only == "c1":
         args.big, args.cpu_baseline = False, False
     if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.force_dist:

@@ -125,3 +125,71 @@ def test_live_counters_overlay_the_committed_profile(bench, monkeypatch):
                         {"item": {"ms": 1.0, "nnz": 1000, "rows": 10,
                                   "parts": [("gram_solve_w1_kernel<true>", 640)]}}, 128, True)
     assert r2["counters_source"].startswith("profiles/pmc_summary.json")
+
+
+def test_dump_outputs_writes_float32_tables_within_the_budget(bench, tmp_path, monkeypatch):
+    """Under the byte budget every row is written; past it each table keeps the same
+    seeded, sorted row sample on every call and names its rows beside it."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(0)
+    U, V = torch.randn(301, 8, generator=g), torch.randn(97, 8, generator=g)
+    rec = bench.dump_outputs(str(tmp_path / "all"), {"user_factors": U, "item_factors": V})
+    got = np.load(tmp_path / "all" / "user_factors.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, U.numpy())
+    assert np.array_equal(np.load(tmp_path / "all" / "item_factors.npy"), V.numpy())
+    assert rec["user_factors"] == {"shape": [301, 8], "of_rows": 301, "dtype": "float32"}
+    assert not (tmp_path / "all" / "user_factors_rows.npy").exists()
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"user_factors": U, "item_factors": V})
+    total = 0
+    for name, full in (("user_factors", U), ("item_factors", V)):
+        x = np.load(tmp_path / "a" / f"{name}.npy")
+        rows = np.load(tmp_path / "a" / f"{name}_rows.npy")
+        assert x.dtype == np.float32 and rows.dtype == np.float64
+        assert 0 < len(rows) < full.shape[0] and np.all(np.diff(rows) > 0)
+        assert np.array_equal(x, full.numpy()[rows.astype(np.int64)])
+        assert np.array_equal(rows, np.load(tmp_path / "b" / f"{name}_rows.npy"))
+        assert np.array_equal(x, np.load(tmp_path / "b" / f"{name}.npy"))
+        total += x.nbytes + rows.nbytes
+    assert 2000 < total <= 4000
+
+
+def test_bench_rejects_zero_steps():
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"],
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode == 2 and "--steps" in p.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_fitted_factors(tmp_path):
+    """A plain run prints the headline line without the --full legs and writes the
+    factor tables of its last timed step (BASELINE configs[0] shape, 3 timed steps)."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps",
+                        "3", "--warmup", "1", "--config", "ml_latest_small", "--dump-outputs",
+                        str(tmp_path / "out")], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = p.stdout.strip().splitlines()
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["full"] is False
+    assert d["unit"] == "ratings/s" and d["higher_is_better"] is True and d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(d["config"]["nnz"] / (d["ms_per_step"] * 1e-3))
+    for moved in ("topk10_ms", "train_rmse", "live_counters", "configs2", "configs3", "configs4"):
+        assert moved not in d
+    assert d["cpu_baseline"] is None
+    assert "fp64_rescued_rows_per_half_sweep" not in d["roofline"]
+    U = np.load(tmp_path / "out" / "user_factors.npy")
+    V = np.load(tmp_path / "out" / "item_factors.npy")
+    assert U.dtype == np.float32 and V.dtype == np.float32
+    assert U.shape == (d["config"]["n_users"], 64) and V.shape == (d["config"]["n_items"], 64)
+    assert np.isfinite(U).all() and np.isfinite(V).all() and np.abs(U).max() > 0

@@ -432,6 +432,9 @@ def _surface_worker(rank, world, port, out_dir):
     from als_mi355x.ml.recommendation import ALS as MLALS
     from als_mi355x.mllib.recommendation import ALS as MLlibALS
     Dm.HipKernels = lambda device, chunk=None: OracleKernels()  # no GPU here
+    # ... also on a host that has one: the oracle kernels are host code, so the engine's
+    # default device (this worker process only) must be the CPU
+    torch.cuda.is_available = lambda: False
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)

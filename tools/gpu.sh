@@ -3,7 +3,7 @@
 #   bash tools/gpu.sh TAG STEP [STEP ...]
 # STEP: tests            the GPU parity suite (errors -> $OUT/errors.jsonl)
 #       tests:EXPR       the suite filtered by pytest -k EXPR
-#       bench            the driver's command: bench.py --gpus 1 --steps 20 --warmup 5
+#       bench            every workload: bench.py --gpus 1 --steps 20 --warmup 5 --full
 #       bench:ARGS       bench.py with ARGS (comma-separated, e.g. bench:--only,c3)
 #       prof             the driver's command under rocprofv3 --kernel-trace --stats
 #       smoke            __graft_entry__.smoke()
@@ -28,7 +28,7 @@ for s in "$@"; do
       [ $rc -eq 0 ] || exit $rc ;;
     bench|bench:*)
       A=${s#bench}; A=${A#:}; A=${A//,/ }
-      [ -z "$A" ] && A="--gpus 1 --steps 20 --warmup 5"
+      [ -z "$A" ] && A="--gpus 1 --steps 20 --warmup 5 --full"
       timeout -k 10 900 python -u bench.py $A > $OUT/bench$n.json 2> $OUT/bench$n.err || { tail -5 $OUT/bench$n.err; exit 1; }
       python3 tools/bench_summary.py $OUT/bench$n.json ;;
     prof)
