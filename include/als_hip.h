@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define ALS_ABI_VERSION 6
+#define ALS_ABI_VERSION 7
 
 #define ALS_OK 0
 #define ALS_EINVAL (-1)   /* bad argument (shape, null pointer, rank) */
@@ -204,18 +204,46 @@ int als_rmse_partial(const int32_t* u, const int32_t* i, const float* r, int64_t
  * top: V is swept with hi.hi alone against the row's k-th score minus a proven
  * bound on the dropped terms, and blocks past it get the full hi.hi + hi.lo + lo.hi
  * score, so every listed pair carries its exact split score.  Lists: registers of
- * one owner lane for top <= 16; for top <= 128 the running top scores in four-lane
- * ("quad") register lists and every key reaching the row's k-th score in a per-row
- * log in the workspace, from which the exact top keys are selected; sorted LDS lists
- * above.  Rows of V holding NaN score NaN and are never listed.
+ * one owner lane for top <= 16; for 16 < top <= 128 every key reaching the row's
+ * threshold (its exact k-th best score as of the last cut of its log) is appended to a
+ * per-row log in the workspace, from which the exact top keys are selected; sorted LDS
+ * lists above.  Rows of V holding NaN score NaN and are never listed.
  * k <= 128, top <= 256.  The n_q x n_v score matrix is never materialised.
- * Workspace (16-byte aligned): scale words, the hi and lo f16 planes of V in sweep
- * (decreasing norm) order, the order, bucket counts, the scaled row norms and, for
- * 16 < top <= 128, the key logs (1,024 keys per query row of up to 4,096 x 128 rows). */
+ * Workspace (16-byte aligned), sized by als_topk_workspace_bytes: scale words, the hi
+ * and lo f16 planes of V in sweep (decreasing norm) order, the order, bucket counts, the
+ * scaled row norms and, for 16 < top <= 128, the key logs: one log per query row of one
+ * launch (at most 512 workgroups of 128 or 256 rows; a larger n_q runs as several
+ * launches over the same logs), each holding `top` rounded up to 32, 64, 100 or 128
+ * keys plus one V tile's worth (192 or 384), at least 384, rounded up to 64. */
 size_t als_topk_workspace_bytes(int64_t n_q, int64_t n_v, int32_t k, int32_t top);
 int als_topk(const float* Q, int64_t n_q, const float* V, int64_t n_v,
              int32_t ld, int32_t k, int32_t top,
              int32_t* idx_out, float* score_out, void* ws, size_t ws_bytes, void* stream);
+
+/* als_topk over the admissible rows of V only (ABI 7; the reference's "movies the user
+ * has not rated, with more than 75 ratings" at RecommenderSystem.py:229 and :245).  V row
+ * j may be listed by query row r only if
+ *  - j is not in ex_col[ex_begin[r] .. ex_end[r]) — dense V rows, ascending within the
+ *    range, duplicates allowed; ranges may be empty and ranges of different rows may
+ *    alias (a subset or slice of query rows points into one shared list).  ex_begin,
+ *    ex_end (n_q entries each) and ex_col are all NULL (no exclusions) or all set;
+ *  - bit (j & 31) of allow_bits[j >> 5] is set (ceil(n_v / 32) words); NULL allows every
+ *    row.
+ * Per query row the `top` admissible rows (allowed, not excluded, score not NaN) by
+ * score descending then index ascending; the remaining slots hold idx -1, score -inf.
+ * An all-zero query row lists its first `top` admissible rows by index with score 0.
+ * Scales, split and summation do not depend on the filter: a pair listed by both calls
+ * carries the bit-identical score.  An admissibility test (the bit, then a binary search
+ * of the row's range) runs only for a pair whose exact score reaches its row's current
+ * threshold, so the thresholds are k-th scores among admissible keys and the coarse
+ * filter stays exact.  Same workspace and argument rules as als_topk; with all four
+ * filter pointers NULL the call is als_topk. */
+int als_topk_filtered(const float* Q, int64_t n_q, const float* V, int64_t n_v,
+                      int32_t ld, int32_t k, int32_t top,
+                      const int64_t* ex_begin, const int64_t* ex_end, const int32_t* ex_col,
+                      const uint32_t* allow_bits,
+                      int32_t* idx_out, float* score_out,
+                      void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -70,9 +70,11 @@ SIGNATURES = {
                                         P]),
     "als_topk_workspace_bytes": (SZ, [I64, I64, I32, I32]),
     "als_topk": (ctypes.c_int, [P, I64, P, I64, I32, I32, I32, P, P, P, SZ, P]),
+    "als_topk_filtered": (ctypes.c_int, [P, I64, P, I64, I32, I32, I32, P, P, P, P, P, P, P, SZ,
+                                         P]),
 }
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 
 class ALSNativeError(RuntimeError):

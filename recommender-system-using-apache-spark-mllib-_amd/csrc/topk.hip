@@ -54,6 +54,7 @@ __device__ __forceinline__ void tk_split(float t, _Float16& hi, _Float16& lo) {
   lo = (_Float16)(t - (float)hi);
 }
 
+#ifndef ALS_TOPK_FILTERED_TU
 // max |x| over n floats -> *out (ordered uint bits; *out zeroed beforehand).
 __global__ __launch_bounds__(256) void tk_absmax_kernel(const float* __restrict__ x, int64_t n,
                                                         unsigned* __restrict__ out) {
@@ -83,6 +84,7 @@ __global__ __launch_bounds__(256) void tk_absmax_kernel(const float* __restrict_
     atomicMax(out, __float_as_uint(m));  // NaN-free non-negative floats order as uints
   }
 }
+#endif  // ALS_TOPK_FILTERED_TU
 
 }  // namespace
 
@@ -107,6 +109,100 @@ constexpr uint64_t kTkKeySentinel = ~0ull;      // entries past `top`: nothing r
 
 __device__ __forceinline__ bool beats(float s1, int i1, float s2, int i2) {
   return s1 > s2 || (s1 == s2 && i1 < i2);
+}
+
+// Filtered top-k (als_topk_filtered): V row j may be listed by query row r only if bit j
+// of `allow` is set (null: every row) and j is not in ex_col[ex_begin[r] .. ex_end[r])
+// (ascending, duplicates allowed; null: no exclusions).  The arrays are indexed by the
+// launch's query rows (the host offsets ex_begin / ex_end with Q for a sliced launch).
+struct TkFilt {
+  const int64_t* ex_begin;
+  const int64_t* ex_end;
+  const int32_t* ex_col;
+  const uint32_t* allow;
+};
+
+__device__ __forceinline__ bool tk_admit(const TkFilt& f, int64_t row, int j) {
+  if (f.allow && !((f.allow[j >> 5] >> (j & 31)) & 1u)) return false;
+  if (!f.ex_begin) return true;
+  const int64_t end = f.ex_end[row];
+  int64_t lo = f.ex_begin[row], hi = end;
+  while (lo < hi) {  // lower bound of j in the row's range (one exit: no return inside)
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (f.ex_col[mid] < j) lo = mid + 1;
+    else hi = mid;
+  }
+  return !(lo < end && f.ex_col[lo] == j);
+}
+
+// An all-zero query row under a filter: every score is 0, so its list is the first `top`
+// admissible V rows by index (the unfiltered rule restricted to them), the rest open.
+// One wave scans 64 V rows per step.
+__device__ __forceinline__ void tk_zero_row_filtered(const TkFilt& f, int64_t row, int64_t n_v,
+                                                     int top, int32_t* __restrict__ idx_out,
+                                                     float* __restrict__ score_out) {
+  const int lane = threadIdx.x & 63;
+  int cnt = 0;
+  for (int64_t base = 0; base < n_v && cnt < top; base += 64) {
+    const int64_t j = base + lane;
+    const bool ok = j < n_v && tk_admit(f, row, (int)j);
+    const uint64_t b = __ballot(ok);
+    const int pos = cnt + __popcll(b & ((1ull << lane) - 1));
+    if (ok && pos < top) {
+      idx_out[row * top + pos] = (int32_t)j;
+      score_out[row * top + pos] = 0.f;
+    }
+    cnt += __popcll(b);
+  }
+  for (int e = (cnt < top ? cnt : top) + lane; e < top; e += 64) {
+    idx_out[row * top + e] = -1;
+    score_out[row * top + e] = -__builtin_inff();
+  }
+}
+
+// The all-zero query rows among a wave's 16 RG rows (row0 + gr g + rho; live[g] bit rho
+// clear and the row present; live is wave-uniform).
+template <int RG>
+__device__ __forceinline__ void tk_zero_rows_filtered(const TkFilt& f, const unsigned (&live)[RG],
+                                                      int64_t row0, int gr, int64_t n_q,
+                                                      int64_t n_v, int top,
+                                                      int32_t* __restrict__ idx_out,
+                                                      float* __restrict__ score_out) {
+#pragma unroll
+  for (int g = 0; g < RG; ++g)
+    for (int rho = 0; rho < 16; ++rho) {
+      const int64_t row = row0 + gr * g + rho;
+      if (row < n_q && !((live[g] >> rho) & 1u))
+        tk_zero_row_filtered(f, row, n_v, top, idx_out, score_out);
+    }
+}
+
+// A refined 16 x 16 block per row group (acc[g][r] = exact score of query row
+// row0 + gr g + r, r = 0..3 of this lane's quarter, against V row j): the pairs that would
+// go on to a list or log (score at or above th[g][r]; all: every pair, while lists are
+// still filling) and are inadmissible score NaN from here on.  Dead rows (absent: no
+// exclusion range to read; or all zero) likewise.
+template <int RG, class TH>
+__device__ __forceinline__ void tk_drop_inadmissible(const TkFilt& f, floatx4 (&acc)[RG], int j,
+                                                     const TH& th, bool all,
+                                                     const unsigned (&live)[RG], int64_t row0,
+                                                     int gr) {
+  const int q = (threadIdx.x & 63) >> 4;
+#pragma unroll
+  for (int g = 0; g < RG; ++g)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      // the verdict as a flag and one select after the branch (with `acc[g][r] = NaN`
+      // assigned inside the branch, the gfx950 code hipcc 7 generated restored the
+      // score for every lane that ran the test: seen in the assembly, and as excluded
+      // rows listed on the device)
+      bool drop = false;
+      if (acc[g][r] == acc[g][r] && (all || acc[g][r] >= th[g][r])) {
+        const bool lv = (live[g] >> (4 * q + r)) & 1u;
+        drop = !lv || !tk_admit(f, row0 + gr * g + r, j);
+      }
+      acc[g][r] = drop ? __builtin_nanf("") : acc[g][r];
+    }
 }
 
 // Offer one 16 x 16 score block to the sorted per-row lists (64-bit keys, best
@@ -203,13 +299,15 @@ __device__ __forceinline__ void topk_write(const uint64_t* __restrict__ lk,
                                            const int* __restrict__ len, int slot0, int64_t qbase,
                                            int64_t n_q, int64_t n_v, int top, float unscale,
                                            unsigned live, int32_t* __restrict__ idx_out,
-                                           float* __restrict__ score_out) {
+                                           float* __restrict__ score_out,
+                                           bool zero_rows = true) {
   const int lane = threadIdx.x & 63;
   for (int rr = 0; rr < 16; ++rr) {
     const int slot = slot0 + rr;
     const int64_t row = qbase + slot;
     if (row >= n_q) break;
     if (!((live >> rr) & 1u)) {  // all-zero query row: every score is 0, ties by index
+      if (!zero_rows) continue;  // (filtered: tk_zero_row_filtered writes them)
       for (int e = lane; e < top; e += 64) {
         idx_out[row * top + e] = e < n_v ? e : -1;
         score_out[row * top + e] = e < n_v ? 0.f : -__builtin_inff();
@@ -231,6 +329,7 @@ __device__ __forceinline__ void topk_write(const uint64_t* __restrict__ lk,
 // The order only affects speed: insertion compares (score, V row index) exactly.
 constexpr int kTkBuckets = 4096;
 
+#ifndef ALS_TOPK_FILTERED_TU  // V's preparation kernels: topk.hip's translation unit only
 // 16 lanes per V row: squared norm -> bucket (0 = largest norms).
 __device__ __forceinline__ int tk_row_bucket(const float* __restrict__ V, int64_t r, int ld,
                                              int k, float log2_ref) {
@@ -381,6 +480,8 @@ __global__ __launch_bounds__(256) void topk_split_table_kernel(const float* __re
     out[total + e] = l;
   }
 }
+
+#endif  // ALS_TOPK_FILTERED_TU
 
 // Split-f16 scores.  NK = KQ / 32 MFMA k-steps (KQ = k padded to 32, 64 or 128);
 // RG query-row groups of 16 NW rows per workgroup (NW wavefronts, tk_nw).
@@ -550,8 +651,27 @@ __device__ __forceinline__ uint64_t tk_log_kth(const uint64_t (&kv)[J], int T) {
 // (Quad lists with two row groups, one wavefront per SIMD, measured round 4 at
 // configs[4]'s 262,144-user sample: top-100 390 ms vs 233 ms with one group.)
 __host__ __device__ constexpr int tk_nw(int topr) { return topr > 0 ? 8 : 4; }
+// FILT (topk_split_filt_kernel, als_topk_filtered): a refined pair that would reach its
+// row's list or log is first tested for admissibility (tk_admit: one bit test and a
+// binary search in the row's exclusion range) and an inadmissible one has its exact
+// score replaced by NaN, which no list, log or threshold accepts — the same treatment
+// as a V row past n_v.  The thresholds therefore are k-th best scores among admissible
+// keys only and the coarse-filter and early-exit bounds hold as stated: both only need
+// a threshold to be a score that `top` listed keys reach.  Scales, split and MFMA
+// order do not depend on the filter, so a pair's score is bit-identical with and
+// without one.  The filtered kernel is this same source compiled in a translation unit
+// of its own (topk_filtered.hip defines ALS_TOPK_FILTERED_TU) under another name and
+// with the filter as a last parameter; in topk.hip's unit FILT is false and every
+// filter statement is discarded, so the unfiltered kernels are untouched by it.
+#ifdef ALS_TOPK_FILTERED_TU
+#define ALS_TOPK_KERNEL topk_split_filt_kernel
+#define ALS_TOPK_FILT_PARAM , TkFilt flt
+#else
+#define ALS_TOPK_KERNEL topk_split_kernel
+#define ALS_TOPK_FILT_PARAM
+#endif
 template <int NK, int RG, int TOPR>
-__global__ __launch_bounds__(64 * tk_nw(TOPR)) void topk_split_kernel(const float* __restrict__ Q, int64_t n_q,
+__global__ __launch_bounds__(64 * tk_nw(TOPR)) void ALS_TOPK_KERNEL(const float* __restrict__ Q, int64_t n_q,
                                                          const uint4* __restrict__ Vsp,
                                                          const uint4* __restrict__ Vlo,
                                                          const int32_t* __restrict__ perm,
@@ -560,7 +680,14 @@ __global__ __launch_bounds__(64 * tk_nw(TOPR)) void topk_split_kernel(const floa
                                                          const float* __restrict__ scal,
                                                          int32_t* __restrict__ idx_out,
                                                          float* __restrict__ score_out,
-                                                         uint64_t* __restrict__ tlog) {
+                                                         uint64_t* __restrict__ tlog
+                                                         ALS_TOPK_FILT_PARAM) {
+#ifdef ALS_TOPK_FILTERED_TU
+  constexpr bool FILT = true;
+#else
+  constexpr bool FILT = false;
+  constexpr TkFilt flt{};  // (named by the discarded FILT statements only)
+#endif
   constexpr int NW = tk_nw(TOPR);  // wavefronts
   constexpr int GR = 16 * NW;          // query rows of a row group
   constexpr int KQ = 32 * NK;
@@ -808,6 +935,7 @@ __global__ __launch_bounds__(64 * tk_nw(TOPR)) void topk_split_kernel(const floa
         for (int r = 0; r < 4; ++r) dmax = fmaxf(dmax, acc[g][r] - ts[g][r]);
       if (__ballot(dmax >= 0.f) == 0) return;
       refine(tbr, ibase, acc);
+      if constexpr (FILT) tk_drop_inadmissible<RG>(flt, acc, bperm[m], tx, false, live, qbase + 16 * w + 4 * q, GR);
       const unsigned below = (1u << m) - 1u;
 #pragma unroll
       for (int g = 0; g < RG; ++g)
@@ -835,6 +963,7 @@ __global__ __launch_bounds__(64 * tk_nw(TOPR)) void topk_split_kernel(const floa
         if (__ballot(dmax >= 0.f) == 0) return;
       }
       refine(tbr, ibase, acc);
+      if constexpr (FILT) tk_drop_inadmissible<RG>(flt, acc, bperm[m], ts, !fullw, live, qbase + 16 * w + 4 * q, GR);
       bool pr[RG][4];
 #pragma unroll
       for (int g = 0; g < RG; ++g)
@@ -886,6 +1015,7 @@ __global__ __launch_bounds__(64 * tk_nw(TOPR)) void topk_split_kernel(const floa
       if (__ballot(vin && dmax >= 0.f) == 0) return;
     }
     refine(tbr, ibase, acc);
+    if constexpr (FILT) tk_drop_inadmissible<RG>(flt, acc, bperm[m], ts, !full, live, qbase + 16 * w + 4 * q, GR);
 #pragma unroll
     for (int g = 0; g < RG; ++g) {
       bool hit = !full;
@@ -1078,6 +1208,10 @@ __global__ __launch_bounds__(64 * tk_nw(TOPR)) void topk_split_kernel(const floa
         const int64_t row = qbase + GR * g + 16 * w + rho;
         if (row >= n_q) break;
         if (!((live[g] >> rho) & 1u)) {  // every score 0: the first `top` rows, ties by index
+          if constexpr (FILT) {
+            tk_zero_row_filtered(flt, row, n_v, top, idx_out, score_out);
+            continue;
+          }
           for (int e = lane; e < top; e += 64) {
             idx_out[row * top + e] = e < n_v ? e : -1;
             score_out[row * top + e] = e < n_v ? 0.f : -__builtin_inff();
@@ -1127,8 +1261,10 @@ __global__ __launch_bounds__(64 * tk_nw(TOPR)) void topk_split_kernel(const floa
           if (j < top) {
             const int e = top - 1 - j;
             if (zero) {  // every score 0: the first `top` rows, ties by index
-              idx_out[row * top + e] = e < n_v ? e : -1;
-              score_out[row * top + e] = e < n_v ? 0.f : -__builtin_inff();
+              if constexpr (!FILT) {  // (FILT: tk_zero_rows_filtered below)
+                idx_out[row * top + e] = e < n_v ? e : -1;
+                score_out[row * top + e] = e < n_v ? 0.f : -__builtin_inff();
+              }
             } else {
               const bool real = kv[0][j] != kTkKeyOpen;
               idx_out[row * top + e] = real ? tk_key_index(kv[0][j]) : -1;
@@ -1138,12 +1274,16 @@ __global__ __launch_bounds__(64 * tk_nw(TOPR)) void topk_split_kernel(const floa
         }
       }
     }
+    if constexpr (FILT)
+      tk_zero_rows_filtered<RG>(flt, live, qbase + 16 * w, GR, n_q, n_v, top, idx_out, score_out);
     return;
   }
 #pragma unroll
   for (int g = 0; g < RG; ++g)
     topk_write(lk, len, GR * g + 16 * w, qbase, n_q, n_v, top, unscale, live[g], idx_out,
-               score_out);
+               score_out, !FILT);
+  if constexpr (FILT)
+    tk_zero_rows_filtered<RG>(flt, live, qbase + 16 * w, GR, n_q, n_v, top, idx_out, score_out);
 }
 
 static int topk_kq(int k) { return k <= 32 ? 32 : (k <= 64 ? 64 : 128); }
@@ -1200,9 +1340,111 @@ static int topk_split_rg(int k, int top, bool logs, int64_t n_q) {
   return 0;
 }
 
+// The sweep's launch: the prepared workspace pieces and the kernel shape chosen by the
+// host entry point.
+struct TkLaunch {
+  const float* Q;
+  int64_t n_q;
+  const uint4* vsp4;  // hi plane
+  const uint4* vlo4;  // lo plane
+  const int32_t* perm;
+  const float* vnorm;
+  int64_t n_v;
+  int ld, k, top;
+  const float* scal;
+  int32_t* idx_out;
+  float* score_out;
+  uint64_t* tlog;
+  size_t lds;
+  int nw, rg, kq;  // wavefronts per workgroup, row groups, padded rank
+  bool logs;
+  hipStream_t st;
+};
+
+// Dispatch over (NK, RG, TOPR) to this translation unit's kernels: topk_split_kernel in
+// topk.hip (f unused), topk_split_filt_kernel in topk_filtered.hip.  Two units, so the
+// unfiltered code objects are what they were before the filter existed and the two sets
+// of 48 instantiations compile side by side.
+#ifdef ALS_TOPK_FILTERED_TU
+#define ALS_TOPK_FILT_ARG , fs
+#else
+#define ALS_TOPK_FILT_ARG
+#endif
+static int topk_launch_split(const TkLaunch& a, const TkFilt& f) {
+  const int64_t rows_blk = 16 * (int64_t)a.nw * a.rg;
+  const int64_t n_blk = (a.n_q + rows_blk - 1) / rows_blk;
+  // key logs: launches of at most kTkLogBlocks blocks (one log slab per block)
+  const int64_t blk_per = a.logs ? (int64_t)kTkLogBlocks : n_blk;
+  const int top = a.top;
+#define ALS_TOPK_SPLIT_LAUNCH2(NK, RG, TR)                                                      \
+  do {                                                                                          \
+    ALS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ALS_TOPK_KERNEL<NK, RG, TR>),    \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds));       \
+    for (int64_t b0 = 0; b0 < n_blk; b0 += blk_per) {                                           \
+      const int64_t r0 = b0 * rows_blk;                                                         \
+      const int64_t nq_c = std::min<int64_t>(a.n_q - r0, blk_per * rows_blk);                   \
+      const unsigned grid = (unsigned)((nq_c + rows_blk - 1) / rows_blk);                       \
+      TkFilt fs = f; /* the slice's rows: exclusion ranges offset as Q and the outputs */       \
+      if (fs.ex_begin) {                                                                        \
+        fs.ex_begin += r0;                                                                      \
+        fs.ex_end += r0;                                                                        \
+      }                                                                                         \
+      (void)fs;                                                                                 \
+      ALS_TOPK_KERNEL<NK, RG, TR><<<grid, 64 * a.nw, a.lds, a.st>>>(                            \
+          a.Q + r0 * a.ld, nq_c, a.vsp4, a.vlo4, a.perm, a.vnorm, a.n_v, a.ld, a.k, top,        \
+          a.scal, a.idx_out + r0 * top, a.score_out + r0 * top, a.tlog ALS_TOPK_FILT_ARG);      \
+      ALS_LAUNCH_CHECK();                                                                       \
+    }                                                                                           \
+  } while (0)
+#define ALS_TOPK_SPLIT_LAUNCH(NK, RG)                 \
+  do {                                                \
+    if (top <= 8)                                     \
+      ALS_TOPK_SPLIT_LAUNCH2(NK, RG, 8);              \
+    else if (top <= 12)                               \
+      ALS_TOPK_SPLIT_LAUNCH2(NK, RG, 12);             \
+    else if (top <= kTopR)                            \
+      ALS_TOPK_SPLIT_LAUNCH2(NK, RG, kTopR);          \
+    else if (!a.logs)                                 \
+      ALS_TOPK_SPLIT_LAUNCH2(NK, RG, 0);              \
+    else if (top <= 32)                               \
+      ALS_TOPK_SPLIT_LAUNCH2(NK, RG, 32);             \
+    else if (top <= 64)                               \
+      ALS_TOPK_SPLIT_LAUNCH2(NK, RG, 64);             \
+    else if (top <= 100)                              \
+      ALS_TOPK_SPLIT_LAUNCH2(NK, RG, 100);            \
+    else                                              \
+      ALS_TOPK_SPLIT_LAUNCH2(NK, RG, kTopQ);          \
+  } while (0)
+  if (a.kq == 32) {
+    if (a.rg == 2) ALS_TOPK_SPLIT_LAUNCH(1, 2);
+    else ALS_TOPK_SPLIT_LAUNCH(1, 1);
+  } else if (a.kq == 64) {
+    if (a.rg == 2) ALS_TOPK_SPLIT_LAUNCH(2, 2);
+    else ALS_TOPK_SPLIT_LAUNCH(2, 1);
+  } else {
+    if (a.rg == 2) ALS_TOPK_SPLIT_LAUNCH(4, 2);
+    else ALS_TOPK_SPLIT_LAUNCH(4, 1);
+  }
+#undef ALS_TOPK_SPLIT_LAUNCH
+#undef ALS_TOPK_SPLIT_LAUNCH2
+#undef ALS_TOPK_FILT_ARG
+  return ALS_OK;
+}
+
+// The filtered instantiations (topk_filtered.hip).
+int topk_launch_filtered(const TkLaunch& a, const TkFilt& f);
+
 }  // namespace als
 
 using namespace als;
+
+#ifdef ALS_TOPK_FILTERED_TU
+
+int als::topk_launch_filtered(const TkLaunch& a, const TkFilt& f) {
+  return topk_launch_split(a, f);
+}
+
+#else
 
 extern "C" {
 
@@ -1230,9 +1472,11 @@ size_t als_topk_workspace_bytes(int64_t n_q, int64_t n_v, int32_t k, int32_t top
          align_up(4 * (size_t)kTkBuckets) + tk_log_bytes(n_q, k, top);
 }
 
-int als_topk(const float* Q, int64_t n_q, const float* V, int64_t n_v, int32_t ld, int32_t k,
-             int32_t top, int32_t* idx_out, float* score_out, void* ws, size_t ws_bytes,
-             void* stream) {
+// als_topk (flt null) and als_topk_filtered share the argument checks, the workspace
+// and V's preparation; only the sweep kernel differs.
+static int topk_run(const float* Q, int64_t n_q, const float* V, int64_t n_v, int32_t ld,
+                    int32_t k, int32_t top, int32_t* idx_out, float* score_out, void* ws,
+                    size_t ws_bytes, void* stream, const TkFilt* flt) {
   ALS_REQUIRE(k >= 1 && k <= 128, ALS_EUNSUPPORTED, "als_topk: rank %d not in [1, 128]", k);
   ALS_REQUIRE(ld >= k && ld % 4 == 0, ALS_EINVAL, "als_topk: bad ld");
   ALS_REQUIRE(top >= 1 && top <= kTopkMax, ALS_EUNSUPPORTED, "als_topk: top %d not in [1, %d]",
@@ -1287,60 +1531,32 @@ int als_topk(const float* Q, int64_t n_q, const float* V, int64_t n_v, int32_t l
         V, n_v, ld, k, scal, perm, vnorm);
     ALS_LAUNCH_CHECK();
   }
-  const size_t lds = topk_split_lds_bytes(kq, rg, top, logs);
-  const int nw = topk_nw(top, logs, rg);  // wavefronts per workgroup
-  const int64_t rows_blk = 16 * (int64_t)nw * rg;
-  const int64_t n_blk = (n_q + rows_blk - 1) / rows_blk;
-  // key logs: launches of at most kTkLogBlocks blocks (one log slab per block)
-  const int64_t blk_per = logs ? (int64_t)kTkLogBlocks : n_blk;
   const uint4* vsp4 = reinterpret_cast<const uint4*>(vsp);
-  const uint4* vlo4 = vsp4 + n_v * (kq / 8);  // lo plane
-#define ALS_TOPK_SPLIT_LAUNCH2(NK, RG, TR)                                                      \
-  do {                                                                                          \
-    ALS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&topk_split_kernel<NK, RG, TR>),  \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));         \
-    for (int64_t b0 = 0; b0 < n_blk; b0 += blk_per) {                                           \
-      const int64_t r0 = b0 * rows_blk;                                                         \
-      const int64_t nq_c = std::min<int64_t>(n_q - r0, blk_per * rows_blk);                     \
-      const unsigned grid = (unsigned)((nq_c + rows_blk - 1) / rows_blk);                       \
-      topk_split_kernel<NK, RG, TR><<<grid, 64 * nw, lds, st>>>(                                \
-          Q + r0 * ld, nq_c, vsp4, vlo4, perm, vnorm, n_v, ld, k, top, scal, idx_out + r0 * top, \
-          score_out + r0 * top, tlog);                                                          \
-      ALS_LAUNCH_CHECK();                                                                       \
-    }                                                                                           \
-  } while (0)
-#define ALS_TOPK_SPLIT_LAUNCH(NK, RG)                 \
-  do {                                                \
-    if (top <= 8)                                     \
-      ALS_TOPK_SPLIT_LAUNCH2(NK, RG, 8);              \
-    else if (top <= 12)                               \
-      ALS_TOPK_SPLIT_LAUNCH2(NK, RG, 12);             \
-    else if (top <= kTopR)                            \
-      ALS_TOPK_SPLIT_LAUNCH2(NK, RG, kTopR);          \
-    else if (!logs)                                   \
-      ALS_TOPK_SPLIT_LAUNCH2(NK, RG, 0);              \
-    else if (top <= 32)                               \
-      ALS_TOPK_SPLIT_LAUNCH2(NK, RG, 32);             \
-    else if (top <= 64)                               \
-      ALS_TOPK_SPLIT_LAUNCH2(NK, RG, 64);             \
-    else if (top <= 100)                              \
-      ALS_TOPK_SPLIT_LAUNCH2(NK, RG, 100);            \
-    else                                              \
-      ALS_TOPK_SPLIT_LAUNCH2(NK, RG, kTopQ);          \
-  } while (0)
-  if (kq == 32) {
-    if (rg == 2) ALS_TOPK_SPLIT_LAUNCH(1, 2);
-    else ALS_TOPK_SPLIT_LAUNCH(1, 1);
-  } else if (kq == 64) {
-    if (rg == 2) ALS_TOPK_SPLIT_LAUNCH(2, 2);
-    else ALS_TOPK_SPLIT_LAUNCH(2, 1);
-  } else {
-    if (rg == 2) ALS_TOPK_SPLIT_LAUNCH(4, 2);
-    else ALS_TOPK_SPLIT_LAUNCH(4, 1);
-  }
-#undef ALS_TOPK_SPLIT_LAUNCH
-#undef ALS_TOPK_SPLIT_LAUNCH2
-  return ALS_OK;
+  const TkLaunch a{Q, n_q, vsp4, vsp4 + n_v * (kq / 8), perm, vnorm, n_v, ld, k, top, scal,
+                   idx_out, score_out, tlog, topk_split_lds_bytes(kq, rg, top, logs),
+                   topk_nw(top, logs, rg), rg, kq, logs, st};
+  return flt ? topk_launch_filtered(a, *flt) : topk_launch_split(a, TkFilt{});
+}
+
+int als_topk(const float* Q, int64_t n_q, const float* V, int64_t n_v, int32_t ld, int32_t k,
+             int32_t top, int32_t* idx_out, float* score_out, void* ws, size_t ws_bytes,
+             void* stream) {
+  return topk_run(Q, n_q, V, n_v, ld, k, top, idx_out, score_out, ws, ws_bytes, stream, nullptr);
+}
+
+int als_topk_filtered(const float* Q, int64_t n_q, const float* V, int64_t n_v, int32_t ld,
+                      int32_t k, int32_t top, const int64_t* ex_begin, const int64_t* ex_end,
+                      const int32_t* ex_col, const uint32_t* allow_bits, int32_t* idx_out,
+                      float* score_out, void* ws, size_t ws_bytes, void* stream) {
+  const int n_ex = (ex_begin != nullptr) + (ex_end != nullptr) + (ex_col != nullptr);
+  ALS_REQUIRE(n_ex == 0 || n_ex == 3, ALS_EINVAL,
+              "als_topk_filtered: ex_begin, ex_end and ex_col must all be null or all be set");
+  const TkFilt flt{ex_begin, ex_end, ex_col, allow_bits};
+  // no filter at all: the unfiltered kernel
+  return topk_run(Q, n_q, V, n_v, ld, k, top, idx_out, score_out, ws, ws_bytes, stream,
+                  (n_ex || allow_bits) ? &flt : nullptr);
 }
 
 }  // extern "C"
+
+#endif  // ALS_TOPK_FILTERED_TU

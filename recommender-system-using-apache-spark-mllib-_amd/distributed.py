@@ -44,6 +44,7 @@ import torch
 import torch.distributed as dist
 
 from .engine import id_offset
+from .filters import reject_sharded_filters
 
 
 class HipKernels:
@@ -885,9 +886,11 @@ class ShardedALS:
         sse, n = part.tolist()
         return (math.sqrt(sse / n) if n > 0 else float("nan")), int(n)
 
-    def recommend_all(self, top: int, user_side: bool = True):
+    def recommend_all(self, top: int, user_side: bool = True, *, exclude=None, candidates=None):
         """recommendForAll for THIS rank's rows of one side (its partition), against
-        the replicated other side: (keys, ids [m, t], scores [m, t]); no collective."""
+        the replicated other side: (keys, ids [m, t], scores [m, t]); no collective.
+        exclude / candidates (ALSCore.recommend_all) are not supported here yet."""
+        reject_sharded_filters(exclude, candidates)
         side, loc = (self.users, self.U_loc) if user_side else (self.items, self.V_loc)
         other = self.items if user_side else self.users
         Vd = self._dense(not user_side)
@@ -908,7 +911,9 @@ class ShardedALS:
             return torch.empty(0, dtype=torch.int32, device=self.device), e.int(), e
         return torch.cat(keys), torch.cat(ids), torch.cat(scs)
 
-    def recommend_subset(self, ids, top: int, user_side: bool = True):
+    def recommend_subset(self, ids, top: int, user_side: bool = True, *, exclude=None,
+                         candidates=None):
+        reject_sharded_filters(exclude, candidates)
         side = self.users if user_side else self.items
         other = self.items if user_side else self.users
         keys = torch.unique(self._ids(ids))

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import filters as _filters
 from ._lib import check, ptr, stream_ptr
 
 DEFAULT_CHUNK = 4096  # ratings per heavy-row task (round 5: profiles/r05/ab_chunk*.jsonl)
@@ -462,6 +463,24 @@ def topk_rows(Q: torch.Tensor, n_q: int, V: torch.Tensor, n_v: int, rank: int, t
     return idx, sc
 
 
+def topk_rows_filtered(Q: torch.Tensor, n_q: int, V: torch.Tensor, n_v: int, rank: int, top: int,
+                       ex_begin, ex_end, ex_col, allow_bits):
+    """topk_rows over the admissible rows of V only (als_topk_filtered): query row r may
+    not list the V rows ex_col[ex_begin[r]:ex_end[r]] (int64 / int64 / int32 device
+    tensors, ascending within a row; all three None = no exclusions) nor a row whose bit
+    in allow_bits (int32 words of the uint32 mask; None = every row) is clear.  Slots
+    past a row's admissible rows hold idx -1, score -inf.  All four None: topk_rows."""
+    L = _lib.lib()
+    idx = torch.empty((n_q, top), dtype=torch.int32, device=Q.device)
+    sc = torch.empty((n_q, top), dtype=torch.float32, device=Q.device)
+    w = torch.empty(int(L.als_topk_workspace_bytes(n_q, n_v, rank, top)), dtype=torch.uint8,
+                    device=Q.device)
+    check(L.als_topk_filtered(ptr(Q), n_q, ptr(V), n_v, Q.shape[1], rank, top, ptr(ex_begin),
+                              ptr(ex_end), ptr(ex_col), ptr(allow_bits), ptr(idx), ptr(sc),
+                              ptr(w), w.numel(), stream_ptr(Q.device)), "als_topk_filtered")
+    return idx, sc
+
+
 # ---------------------------------------------------------------------------
 # The engine
 # ---------------------------------------------------------------------------
@@ -514,6 +533,7 @@ class ALSCore:
         self.user_block = build_block(u, self.uidx, i, self.iidx, r, self.ws, chunk)
         self.item_block = build_block(i, self.iidx, u, self.uidx, r, self.ws, chunk)
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._train_ex = {}  # user_side -> sorted training exclusion list (train_exclusion)
         self.U: Optional[torch.Tensor] = None
         self.V: Optional[torch.Tensor] = None
         self.rank = 0
@@ -531,6 +551,7 @@ class ALSCore:
         self.nnz = 0
         self._auto_chunk = False
         self.user_block = self.item_block = None
+        self._train_ex = {}
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
         U = _to_device(U, torch.float32, self.device)
         V = _to_device(V, torch.float32, self.device)
@@ -673,18 +694,96 @@ class ALSCore:
             return self.uidx, self.U, self.iidx, self.V
         return self.iidx, self.V, self.uidx, self.U
 
-    def recommend_all(self, top: int, user_side: bool = True):
+    def train_exclusion(self, user_side: bool = True):
+        """The pairs this core was fitted on as an exclusion list for one side's queries:
+        (row_ptr int64 [n + 1], col int32 [nnz]), row r's other-side dense rows ascending in
+        col[row_ptr[r]:row_ptr[r + 1]] (duplicates kept).  Built once per side and cached.
+        RatingBlock.col is in input order, so the list is made by K1 itself: the OPPOSITE
+        block's CSR, expanded to COO, has the wanted index ascending already, and
+        als_csr_build's sort by this side's row is stable (O(nnz) memory, no 64-bit
+        sort of the ratings)."""
+        got = self._train_ex.get(bool(user_side))
+        if got is not None:
+            return got
+        if self.user_block is None:
+            raise ValueError("exclude='train' needs the ratings the model was fitted on; this "
+                             "core was built from saved factors (from_factors / load) and has "
+                             "none: pass the pairs to exclude explicitly")
+        L = _lib.lib()
+        mine, opp = (self.user_block, self.item_block) if user_side else (self.item_block,
+                                                                          self.user_block)
+        dev = self.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        deg = opp.row_ptr[1:] - opp.row_ptr[:-1]
+        # COO of the opposite block: its row (= the other side's dense row) per entry,
+        # ascending; its col = this side's dense row
+        other = torch.repeat_interleave(torch.arange(opp.n_rows, **i32), deg)
+        row_map = torch.arange(mine.n_rows, **i32)
+        col_map = torch.arange(opp.n_rows, **i32)
+        row_ptr = torch.empty(mine.n_rows + 1, dtype=torch.int64, device=dev)
+        col = torch.empty(max(opp.nnz, 1), **i32)
+        val = torch.empty(max(opp.nnz, 1), dtype=torch.float32, device=dev)  # (unused copy)
+        w = self.ws.get(L.als_csr_workspace_bytes(opp.nnz, mine.n_rows))
+        check(L.als_csr_build(ptr(opp.col), ptr(row_map), ptr(other), ptr(col_map), ptr(opp.val),
+                              opp.nnz, mine.n_rows, ptr(row_ptr), ptr(col), ptr(val), ptr(w),
+                              w.numel(), stream_ptr(dev)), "als_csr_build (exclusion list)")
+        # K1 has no way to skip the values: the fp32 copy and the COO index go as soon as
+        # the sort has run (peak: 3 x 4 B per rating beside the two rating blocks and
+        # K1's workspace; kept: 4 B per rating per side)
+        del val, other
+        self._train_ex[bool(user_side)] = (row_ptr, col)
+        return row_ptr, col
+
+    def _filter_args(self, exclude, candidates, user_side: bool, rows=None):
+        """(ex_begin, ex_end, ex_col, allow_bits) of a filtered top-k over the query rows
+        `rows` (dense, int64; None = every row of the side).  exclude: None, "train", or
+        (query ids, other ids) pairs (host or device; unknown ids dropped, as predict's
+        inner join does); candidates: None or ids of the other side (unknown dropped)."""
+        qi, _, oi, _ = self._sides(user_side)
+        beg = end = col = bits = None
+        if isinstance(exclude, str):
+            if exclude != "train":
+                raise ValueError(f"exclude must be None, 'train' or (ids, ids) pairs, got {exclude!r}")
+            rp, col = self.train_exclusion(user_side)
+            beg, end = rp[:-1], rp[1:]
+        elif exclude is not None:
+            a, b = exclude
+            a = _to_device(a, torch.int32, self.device)
+            b = _to_device(b, torch.int32, self.device)
+            beg, end, col = _filters.exclusion_lists(qi.rows_of(a), oi.rows_of(b), qi.n)
+        if beg is not None:
+            if rows is not None:
+                beg, end = beg[rows], end[rows]
+            beg, end = beg.contiguous(), end.contiguous()
+        if candidates is not None:
+            c = _to_device(candidates, torch.int32, self.device)
+            bits = _filters.pack_allow_bits(oi.rows_of(c), oi.n)
+        return beg, end, col, bits
+
+    def _topk(self, Q, n_q, user_side, top, exclude, candidates, rows=None):
+        _, _, oi, Vo = self._sides(user_side)
+        if exclude is None and candidates is None:
+            return topk_rows(Q, n_q, Vo, oi.n, self.rank, top)
+        return topk_rows_filtered(Q, n_q, Vo, oi.n, self.rank, top,
+                                  *self._filter_args(exclude, candidates, user_side, rows))
+
+    def recommend_all(self, top: int, user_side: bool = True, *, exclude=None, candidates=None):
         """recommendForAll: for every row of one side (dense order) its `top` best
         rows of the other side.  Returns (keys [n], ids [n, t], scores [n, t]) on the
-        device, t = min(top, rows of the other side), scores descending."""
+        device, t = min(top, rows of the other side), scores descending.
+        exclude: pairs a row must not list — "train" (the pairs the core was fitted on)
+        or (query ids, other ids); candidates: ids of the other side the lists are
+        restricted to.  Slots past a row's admissible rows have score -inf."""
         qi, Q, oi, Vo = self._sides(user_side)
-        idx, sc = topk_rows(Q, qi.n, Vo, oi.n, self.rank, top)
+        idx, sc = self._topk(Q, qi.n, user_side, top, exclude, candidates)
         t = min(int(top), oi.n)
         return qi.ids(), ids_of(oi.ids(), idx[:, :t]), sc[:, :t]
 
-    def recommend_subset(self, ids, top: int, user_side: bool = True):
+    def recommend_subset(self, ids, top: int, user_side: bool = True, *, exclude=None,
+                         candidates=None):
         """recommendForUserSubset / ForItemSubset: distinct known ids of `ids`
-        (ascending) -> (keys, ids [m, t], scores [m, t])."""
+        (ascending) -> (keys, ids [m, t], scores [m, t]).  exclude / candidates as
+        recommend_all (the subset's rows point into the one exclusion list)."""
         qi, Q, oi, Vo = self._sides(user_side)
         q = _to_device(ids, torch.int32, self.device)
         keys = torch.unique(q)
@@ -696,7 +795,7 @@ class ALSCore:
             return keys, torch.empty((0, t), dtype=torch.int32, device=self.device), \
                 torch.empty((0, t), dtype=torch.float32, device=self.device)
         Qs = Q.index_select(0, rows.long()).contiguous()
-        idx, sc = topk_rows(Qs, keys.numel(), Vo, oi.n, self.rank, top)
+        idx, sc = self._topk(Qs, keys.numel(), user_side, top, exclude, candidates, rows.long())
         return keys, ids_of(oi.ids(), idx[:, :t]), sc[:, :t]
 
     def recommend_users(self, top: int):

@@ -1,0 +1,66 @@
+"""Host-side inputs of the filtered top-k (als_topk_filtered, include/als_hip.h).
+
+The reference's product lists, per user, the movies the user has NOT rated
+(RecommenderSystem.py:229) among those with more than 75 ratings (R:245).  The
+kernel takes the two conditions as
+  * per-query-row exclusion ranges: ex_col[ex_begin[r] .. ex_end[r]) = dense rows of
+    the other side, ascending within a row, duplicates kept (Spark keeps duplicate
+    ratings), and
+  * one global allow set as a bitmask over the other side's dense rows.
+Everything here is torch on whatever device the inputs live on (the tests run it on
+CPU tensors); nothing launches library code.
+"""
+from __future__ import annotations
+
+import torch
+
+__all__ = ["pack_allow_bits", "exclusion_lists", "reject_sharded_filters"]
+
+
+def pack_allow_bits(rows: torch.Tensor, n_v: int) -> torch.Tensor:
+    """Dense rows (any integer dtype; entries outside [0, n_v), such as the -1 of an
+    unknown id, are dropped; duplicates are fine) -> the allow mask: int32 words holding
+    the uint32 bit patterns, bit (j & 31) of word (j >> 5) set for every row j given,
+    ceil(n_v / 32) words (at least one, so the mask always has an address)."""
+    n_words = max((int(n_v) + 31) // 32, 1)
+    rows = rows.reshape(-1).long()
+    rows = torch.unique(rows[(rows >= 0) & (rows < int(n_v))])
+    words = torch.zeros(n_words, dtype=torch.int64, device=rows.device)
+    # distinct bits of one word add up to their OR
+    words.index_add_(0, rows >> 5, torch.ones_like(rows) << (rows & 31))
+    # the uint32 pattern as int32 (two's complement wrap of bit 31)
+    return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
+
+
+def exclusion_lists(q_rows: torch.Tensor, o_rows: torch.Tensor, n_q: int):
+    """(query dense row, other-side dense row) pairs -> (begin int64 [n_q], end int64
+    [n_q], col int32 [m]): row r's excluded rows are col[begin[r]:end[r]], ascending,
+    duplicates kept; pairs with either row negative (an unknown id) are dropped, rows
+    without pairs get an empty range.  col has at least one element (a null ex_col with
+    non-null ranges is an argument error of the C entry point).
+    One sort of a 64-bit (row, col) key: for caller-supplied pair lists; the training
+    ratings go through ALSCore's K1-based path instead."""
+    q = q_rows.reshape(-1).long()
+    o = o_rows.reshape(-1).long()
+    if q.numel() != o.numel():
+        raise ValueError("exclude: the two id arrays must have the same length")
+    ok = (q >= 0) & (q < int(n_q)) & (o >= 0)
+    q, o = q[ok], o[ok]
+    key = torch.sort((q << 32) | o).values
+    col = (key & 0xFFFFFFFF).to(torch.int32)
+    ptr = torch.zeros(int(n_q) + 1, dtype=torch.int64, device=q.device)
+    if key.numel():
+        ptr[1:] = torch.cumsum(torch.bincount(key >> 32, minlength=int(n_q)), 0)
+    if col.numel() == 0:
+        col = torch.zeros(1, dtype=torch.int32, device=q.device)
+    return ptr[:-1].contiguous(), ptr[1:].contiguous(), col.contiguous()
+
+
+def reject_sharded_filters(exclude, candidates) -> None:
+    """The sharded engine's recommend_all / recommend_subset accept the two keywords and
+    refuse them: filtered serving runs on the single-GPU engine only so far."""
+    if exclude is not None or candidates is not None:
+        raise NotImplementedError(
+            "exclude= / candidates= are not supported by the sharded engine (ShardedALS) yet: "
+            "serve filtered recommendations from a single-GPU ALSCore (e.g. "
+            "ALSCore.from_factors over the gathered factors)")

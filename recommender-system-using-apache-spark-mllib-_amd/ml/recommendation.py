@@ -234,13 +234,37 @@ class ALSModel:
         return rm
 
     # -- recommendForAll (K5) --
-    def recommendForAllUsersArrays(self, numItems: int):
-        """Device tensors (user ids [n_u], item ids [n_u, t], scores [n_u, t]),
-        t = min(numItems, n_items).  Multi-GPU: this rank's users (its partition)."""
-        return self._core.recommend_all(int(numItems), True)
+    def _exclude_arg(self, exclude):
+        """exclude= of the recommend* methods -> the engine's form: None, "train" (the
+        pairs the model was fitted on) or a dataset of (userCol, itemCol) pairs, of any
+        kind transform() takes."""
+        if exclude is None or isinstance(exclude, str):
+            return exclude
+        p = self._p
+        u, i = columns_of(exclude, (p["userCol"], p["itemCol"]))
+        return check_integers(u, p["userCol"]), check_integers(i, p["itemCol"])
 
-    def recommendForAllItemsArrays(self, numUsers: int):
-        return self._core.recommend_all(int(numUsers), False)
+    def _filters(self, exclude, candidates, user_side: bool):
+        ex = self._exclude_arg(exclude)
+        if isinstance(ex, tuple) and not user_side:
+            ex = (ex[1], ex[0])  # the engine takes (query ids, other ids)
+        if candidates is not None:
+            col = self._p["itemCol" if user_side else "userCol"]
+            candidates = check_integers(np.asarray(candidates).reshape(-1), col)
+        return dict(exclude=ex, candidates=candidates)
+
+    def recommendForAllUsersArrays(self, numItems: int, *, exclude=None, candidates=None):
+        """Device tensors (user ids [n_u], item ids [n_u, t], scores [n_u, t]),
+        t = min(numItems, n_items).  Multi-GPU: this rank's users (its partition).
+        exclude: (user, item) pairs never to list — "train" or a dataset with the
+        model's user and item columns; candidates: item ids the lists are restricted
+        to.  Slots past a user's admissible items have score -inf."""
+        return self._core.recommend_all(int(numItems), True,
+                                        **self._filters(exclude, candidates, True))
+
+    def recommendForAllItemsArrays(self, numUsers: int, *, exclude=None, candidates=None):
+        return self._core.recommend_all(int(numUsers), False,
+                                        **self._filters(exclude, candidates, False))
 
     @staticmethod
     def _recs_df(key_col, keys, ids, sc):
@@ -253,21 +277,27 @@ class ALSModel:
                 for ri, rs in zip(ids, sc)]
         return pd.DataFrame({key_col: keys, "recommendations": recs})
 
-    def recommendForAllUsers(self, numItems: int):
+    def recommendForAllUsers(self, numItems: int, *, exclude=None, candidates=None):
         """DataFrame[userCol, recommendations: list of (item, rating)], rating desc
-        (ties: lower item id first)."""
-        return self._recs_df(self._p["userCol"], *self.recommendForAllUsersArrays(numItems))
+        (ties: lower item id first).  exclude="train" leaves out what each user has
+        already rated (the reference's R:229); candidates= restricts the items (its
+        R:245 "more than 75 ratings"); see recommendForAllUsersArrays."""
+        return self._recs_df(self._p["userCol"], *self.recommendForAllUsersArrays(
+            numItems, exclude=exclude, candidates=candidates))
 
-    def recommendForAllItems(self, numUsers: int):
-        return self._recs_df(self._p["itemCol"], *self.recommendForAllItemsArrays(numUsers))
+    def recommendForAllItems(self, numUsers: int, *, exclude=None, candidates=None):
+        return self._recs_df(self._p["itemCol"], *self.recommendForAllItemsArrays(
+            numUsers, exclude=exclude, candidates=candidates))
 
-    def recommendForUserSubset(self, dataset, numItems: int):
+    def recommendForUserSubset(self, dataset, numItems: int, *, exclude=None, candidates=None):
         """Top items for the distinct known users of `dataset[userCol]`."""
         col = self._p["userCol"]
         ids = check_integers(columns_of(dataset, (col,))[0], col)
-        return self._recs_df(col, *self._core.recommend_subset(ids, int(numItems), True))
+        return self._recs_df(col, *self._core.recommend_subset(
+            ids, int(numItems), True, **self._filters(exclude, candidates, True)))
 
-    def recommendForItemSubset(self, dataset, numUsers: int):
+    def recommendForItemSubset(self, dataset, numUsers: int, *, exclude=None, candidates=None):
         col = self._p["itemCol"]
         ids = check_integers(columns_of(dataset, (col,))[0], col)
-        return self._recs_df(col, *self._core.recommend_subset(ids, int(numUsers), False))
+        return self._recs_df(col, *self._core.recommend_subset(
+            ids, int(numUsers), False, **self._filters(exclude, candidates, False)))

@@ -110,22 +110,39 @@ class MatrixFactorizationModel:
         F = F.double().cpu().numpy()
         return [(int(a), tuple(row)) for a, row in zip(ids.cpu().numpy(), F)]
 
-    def _one(self, key, num, user_side):
-        keys, ids, sc = self._core.recommend_subset([int(key)], int(num), user_side)
+    def _filters(self, exclude, candidates, user_side):
+        """exclude: None, "train" or (user, product[, rating]) rows never to list;
+        candidates: ids of the listed side (products for users, users for products)."""
+        if exclude is not None and not isinstance(exclude, str):
+            u, i = _pairs(exclude)
+            exclude = (u, i) if user_side else (i, u)
+        if candidates is not None:
+            candidates = check_integers(np.asarray(candidates).reshape(-1),
+                                        "product" if user_side else "user")
+        return dict(exclude=exclude, candidates=candidates)
+
+    def _one(self, key, num, user_side, exclude=None, candidates=None):
+        keys, ids, sc = self._core.recommend_subset(
+            [int(key)], int(num), user_side, **self._filters(exclude, candidates, user_side))
         if keys.numel() == 0:
             raise KeyError(f"unknown id {key}")
         ids, sc = ids.cpu().numpy()[0], sc.cpu().numpy()[0]
         return [Rating(key, int(a), float(s)) if user_side else Rating(int(a), key, float(s))
                 for a, s in zip(ids, sc) if np.isfinite(s)]
 
-    def recommendProducts(self, user: int, num: int) -> List[Rating]:
-        return self._one(int(user), num, True)
+    def recommendProducts(self, user: int, num: int, *, exclude=None,
+                          candidates=None) -> List[Rating]:
+        """exclude="train" (or (user, product) rows) leaves those pairs out of the list;
+        candidates= restricts the products listed (RecommenderSystem.py:229 / :245)."""
+        return self._one(int(user), num, True, exclude, candidates)
 
-    def recommendUsers(self, product: int, num: int) -> List[Rating]:
-        return self._one(int(product), num, False)
+    def recommendUsers(self, product: int, num: int, *, exclude=None,
+                       candidates=None) -> List[Rating]:
+        return self._one(int(product), num, False, exclude, candidates)
 
-    def recommendProductsForUsers(self, num: int):
-        keys, ids, sc = self._core.recommend_all(int(num), True)
+    def recommendProductsForUsers(self, num: int, *, exclude=None, candidates=None):
+        keys, ids, sc = self._core.recommend_all(int(num), True,
+                                                 **self._filters(exclude, candidates, True))
         keys, ids, sc = keys.cpu().numpy(), ids.cpu().numpy(), sc.cpu().numpy()
         return [(int(k), [Rating(int(k), int(a), float(s)) for a, s in zip(ri, rs)
                           if np.isfinite(s)])
@@ -147,8 +164,9 @@ class MatrixFactorizationModel:
         return cls(_engine.ALSCore.from_factors(uids, U.astype(np.float32), pids,
                                                 V.astype(np.float32)))
 
-    def recommendUsersForProducts(self, num: int):
-        keys, ids, sc = self._core.recommend_all(int(num), False)
+    def recommendUsersForProducts(self, num: int, *, exclude=None, candidates=None):
+        keys, ids, sc = self._core.recommend_all(int(num), False,
+                                                 **self._filters(exclude, candidates, False))
         keys, ids, sc = keys.cpu().numpy(), ids.cpu().numpy(), sc.cpu().numpy()
         return [(int(k), [Rating(int(a), int(k), float(s)) for a, s in zip(ri, rs)
                           if np.isfinite(s)])
