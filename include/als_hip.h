@@ -177,7 +177,9 @@ int als_yty(const float* Y, int64_t n, int32_t ld, int32_t k, double* yty_packed
  *      computeError join+reduce at RecommenderSystem.py:103-129) --------- */
 
 /* pred_out[e] = <U[umap[u[e]]], V[imap[i[e]]]> in fp64 over fp32 factors,
- * NaN when either id is unknown (out of map range or map == -1). */
+ * NaN when either id is unknown (out of map range or map == -1).  K4 (als_predict
+ * and als_rmse_partial) ignores columns [k, ld) of U and V: whatever they hold,
+ * NaN included, never reaches a result. */
 int als_predict(const int32_t* u, const int32_t* i, int64_t n,
                 const int32_t* umap, int32_t umap_size, const int32_t* imap, int32_t imap_size,
                 const float* U, const float* V, int32_t ld, int32_t k,

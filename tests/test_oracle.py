@@ -72,6 +72,35 @@ def test_schedule_oracle_covers_every_rating_once():
     assert slot_begin[-1] == len(chunks)
 
 
+@pytest.mark.parametrize("chunk", [1, 64, 255])
+def test_schedule_oracle_empty_rows_and_chunk_edges(chunk):
+    # the reference of the GPU schedule edge tests: empty rows (first, last, adjacent) and
+    # degrees exactly chunk, chunk + 1, 2 chunk, 2 chunk + 1 — every row scheduled once,
+    # every rating of a heavy row in exactly one task, in slot order
+    deg = np.array([0, chunk, chunk + 1, 0, 0, 2 * chunk, 2 * chunk + 1, 1, chunk,
+                    3 * chunk - 1, chunk + 1, 0])
+    ptr = np.concatenate([[0], np.cumsum(deg)])
+    light, heavy, slot_begin, chunks = O.schedule_build(ptr, chunk)
+    assert sorted(np.concatenate([light, heavy]).tolist()) == list(range(len(deg)))
+    assert np.all(deg[light] <= chunk) and np.all(deg[heavy] > chunk)
+    assert list(heavy) == sorted(heavy)  # heavy rows by row id
+    # LPT order, equal degrees (the empty rows among them) by row id
+    assert list(light) == sorted(light, key=lambda r: (-deg[r], r))
+    covered = np.zeros(ptr[-1], int)
+    for r, b, e in chunks:
+        assert 0 < e - b <= chunk and ptr[r] <= b < e <= ptr[r + 1]
+        covered[b:e] += 1
+    light_mask = np.zeros(ptr[-1], bool)
+    for r in light:
+        light_mask[ptr[r]:ptr[r + 1]] = True
+    assert np.array_equal(covered, (~light_mask).astype(int))  # light ratings in no task
+    want = [(r, b, min(b + chunk, ptr[r + 1])) for r in heavy
+            for b in range(ptr[r], ptr[r + 1], chunk)]
+    assert chunks == want
+    assert list(slot_begin) == [0] + list(np.cumsum(-(-deg[heavy] // chunk)))
+    assert slot_begin[-1] == len(chunks)
+
+
 @pytest.mark.parametrize("rank", [1, 4, 10, 33, 64])
 @pytest.mark.parametrize("implicit", [False, True])
 def test_numpy_oracle_matches_c_restatement(rank, implicit):
