@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define ALS_ABI_VERSION 7
+#define ALS_ABI_VERSION 8
 
 #define ALS_OK 0
 #define ALS_EINVAL (-1)   /* bad argument (shape, null pointer, rank) */
@@ -246,6 +246,37 @@ int als_topk_filtered(const float* Q, int64_t n_q, const float* V, int64_t n_v,
                       const uint32_t* allow_bits,
                       int32_t* idx_out, float* score_out,
                       void* ws, size_t ws_bytes, void* stream);
+
+/* ---- K6: ranking metrics (replaces pyspark.mllib.evaluation.RankingMetrics /
+ *      pyspark.ml.evaluation.RankingEvaluator over the lists K5 writes; the reference
+ *      scores its models by RMSE alone, RecommenderSystem.py:103-129) ---------- */
+
+/* Precision, recall, average precision and NDCG at `at` (ABI 8) of n_q top-k lists
+ * against per-row relevant sets, binary relevance.  idx[r*idx_ld + p], p < at, is the
+ * dense row listed at position p of query row r (the layout als_topk / als_topk_filtered
+ * write; idx_ld >= at); a negative entry is an empty slot and never a hit.
+ * rel_col[rel_begin[r] .. rel_end[r]) holds the relevant rows of r, STRICTLY ascending
+ * (the caller removes duplicates); ranges may be empty and ranges of different rows may
+ * alias, as the ex_* ranges of als_topk_filtered may.  With m_r the range length,
+ * hit(p) = 1 when idx[r, p] is in the range, c(p) the hits at positions 0..p and
+ * H = c(at - 1), a row with m_r > 0 scores
+ *   precision = H / at                  (divided by `at` even when the list is shorter)
+ *   recall    = H / m_r
+ *   AP        = (sum_{p: hit} c(p) / (p + 1)) / min(m_r, at)
+ *   NDCG      = (sum_{p: hit} d(p)) / (sum_{p < min(m_r, at)} d(p)),  d(p) = 1 / log2(p + 2)
+ * which are Spark 3.x's precisionAt, recallAt, meanAveragePrecisionAt and ndcgAt per
+ * row.  A row with m_r = 0 contributes nothing and is not counted.
+ * sums_out[6] = {sum precision, sum recall, sum AP, sum NDCG, rows with m_r > 0, rows
+ * with H > 0}.  per_row_out: NULL, or n_q x 4 fp64 = the four values per row (all 0 for
+ * a row with m_r = 0).  All arithmetic is fp64; the sums within a row run in position
+ * order, and across rows in a fixed order (per-block partials, then one block), so two
+ * calls give bit-identical results.  1 <= at <= 256.  ws: 16-byte aligned, sized by
+ * als_rank_metrics_workspace_bytes.  n_q == 0 writes six zeros. */
+size_t als_rank_metrics_workspace_bytes(int64_t n_q);
+int als_rank_metrics(const int32_t* idx, int64_t n_q, int32_t idx_ld, int32_t at,
+                     const int64_t* rel_begin, const int64_t* rel_end, const int32_t* rel_col,
+                     double* sums_out, double* per_row_out,
+                     void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

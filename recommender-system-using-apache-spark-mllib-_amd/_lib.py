@@ -72,9 +72,11 @@ SIGNATURES = {
     "als_topk": (ctypes.c_int, [P, I64, P, I64, I32, I32, I32, P, P, P, SZ, P]),
     "als_topk_filtered": (ctypes.c_int, [P, I64, P, I64, I32, I32, I32, P, P, P, P, P, P, P, SZ,
                                          P]),
+    "als_rank_metrics_workspace_bytes": (SZ, [I64]),
+    "als_rank_metrics": (ctypes.c_int, [P, I64, I32, I32, P, P, P, P, P, P, SZ, P]),
 }
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 class ALSNativeError(RuntimeError):

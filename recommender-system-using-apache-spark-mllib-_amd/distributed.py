@@ -931,6 +931,14 @@ class ShardedALS:
                               top)
         return keys, other.ids()[idx[:, :t].long().clamp(min=0)], sc[:, :t]
 
+    def rank_metrics(self, users, items, at: int, **kw):
+        """ALSCore.rank_metrics is not offered on the sharded engine yet (as the filters
+        it is usually combined with are not)."""
+        raise NotImplementedError(
+            "rank_metrics is not supported by the sharded engine (ShardedALS) yet: evaluate "
+            "rankings on a single-GPU ALSCore (e.g. ALSCore.from_factors over the gathered "
+            "factors)")
+
     def recommend_users(self, top: int):
         _, ids, sc = self.recommend_all(top, True)
         return ids, sc

@@ -481,6 +481,40 @@ def topk_rows_filtered(Q: torch.Tensor, n_q: int, V: torch.Tensor, n_v: int, ran
     return idx, sc
 
 
+MAX_RANK_AT = 256  # als_rank_metrics: list positions scored per row
+
+
+def rank_metrics_rows(idx: torch.Tensor, at: int, begin, end, col, ws: Workspace,
+                      per_row: bool = False):
+    """K6 over the lists idx (int32 [n_q, >= at], dense rows, negative = empty slot)
+    against the relevant sets col[begin[r]:end[r]] (strictly ascending: filters.
+    relevance_lists).  Returns (sums f64 [6] = sum precision, sum recall, sum AP, sum
+    NDCG, rows with a relevant set, rows with a hit; per-row f64 [n_q, 4] or None)."""
+    L = _lib.lib()
+    if idx.dtype != torch.int32 or idx.dim() != 2 or (idx.shape[1] > 1 and idx.stride(1) != 1):
+        raise ValueError("rank_metrics_rows: idx must be an int32 [n_q, width] tensor with "
+                         "unit stride along a row")
+    if idx.shape[1] < int(at):
+        raise ValueError(f"rank_metrics_rows: lists of width {idx.shape[1]} < at = {at}")
+    n_q = int(idx.shape[0])
+    out = torch.empty(6, dtype=torch.float64, device=idx.device)
+    rows = torch.empty((n_q, 4), dtype=torch.float64, device=idx.device) if per_row else None
+    w = ws.get(L.als_rank_metrics_workspace_bytes(n_q))
+    ld = int(idx.stride(0)) if n_q > 1 else int(idx.shape[1])  # one row: any stride
+    check(L.als_rank_metrics(ptr(idx), n_q, ld, int(at),
+                             ptr(begin), ptr(end), ptr(col), ptr(out), ptr(rows), ptr(w),
+                             w.numel(), stream_ptr(idx.device)), "als_rank_metrics")
+    return out, rows
+
+
+def rank_metrics_dict(sums, rows: int) -> dict:
+    """The means over `rows` query rows of K6's sums (host list of 6); NaN when rows == 0."""
+    def mean(x):
+        return x / rows if rows > 0 else float("nan")
+    return {"precision": mean(sums[0]), "recall": mean(sums[1]), "map": mean(sums[2]),
+            "ndcg": mean(sums[3]), "hitRate": mean(sums[5]), "rows": int(rows)}
+
+
 # ---------------------------------------------------------------------------
 # The engine
 # ---------------------------------------------------------------------------
@@ -797,6 +831,58 @@ class ALSCore:
         Qs = Q.index_select(0, rows.long()).contiguous()
         idx, sc = self._topk(Qs, keys.numel(), user_side, top, exclude, candidates, rows.long())
         return keys, ids_of(oi.ids(), idx[:, :t]), sc[:, :t]
+
+    def rank_metrics(self, users, items, at: int, *, ratings=None, threshold=None,
+                     user_side: bool = True, exclude=None, candidates=None,
+                     per_row: bool = False) -> dict:
+        """Ranking quality of the top-`at` lists against held-out (user, item) pairs:
+        Spark's RankingMetrics precisionAt / recallAt / meanAveragePrecisionAt / ndcgAt
+        (binary relevance), lists and metrics both on the device (K5 then K6).
+        Pairs with an unknown id are dropped (rmse's inner join); with `threshold` only
+        pairs with rating >= threshold are relevant (`ratings` required).  The query
+        rows are the users (items when user_side is False) with at least one relevant
+        pair; their lists come from the recommend path with top = min(at, rows of the
+        other side) and exclude / candidates passed through (exclude="train" scores
+        unseen items only).  Returns {"precision", "recall", "map", "ndcg", "hitRate"
+        (rows with at least one hit), "rows"}: means over `rows`, NaN when rows == 0.
+        per_row: also "keys" (ids of the query rows, ascending) and "per_row"
+        (f64 [rows, 4]: precision, recall, AP, NDCG), both on the device."""
+        qi, Q, oi, _ = self._sides(user_side)
+        at = int(at)
+        if at < 1 or at > MAX_RANK_AT:
+            raise ValueError(f"at must be in [1, {MAX_RANK_AT}], got {at}")
+        u = _to_device(users, torch.int32, self.device)
+        i = _to_device(items, torch.int32, self.device)
+        if u.numel() != i.numel():
+            raise ValueError("users and items must have the same length")
+        q, o = (qi.rows_of(u), oi.rows_of(i)) if user_side else (qi.rows_of(i), oi.rows_of(u))
+        keep = (q >= 0) & (o >= 0)
+        if threshold is not None:
+            if ratings is None:
+                raise ValueError("threshold needs the held-out ratings")
+            r = _to_device(ratings, torch.float32, self.device)
+            if r.numel() != u.numel():
+                raise ValueError("users, items and ratings must have the same length")
+            keep &= r >= float(threshold)
+        rows, inv = torch.unique(q[keep], return_inverse=True)  # ascending dense rows
+        n = int(rows.numel())
+        if n == 0:
+            out = rank_metrics_dict([0.0] * 6, 0)
+            if per_row:
+                out["keys"] = qi.ids()[:0]
+                out["per_row"] = torch.empty((0, 4), dtype=torch.float64, device=self.device)
+            return out
+        beg, end, col = _filters.relevance_lists(inv, o[keep], n)
+        t = min(at, oi.n)
+        Qs = Q.index_select(0, rows).contiguous()
+        idx, _ = self._topk(Qs, n, user_side, t, exclude, candidates, rows)
+        sums, pr = rank_metrics_rows(idx, t, beg, end, col, self.ws, per_row)
+        sums = sums.tolist()
+        out = rank_metrics_dict(sums, int(sums[4]))
+        if per_row:
+            out["keys"] = qi.ids()[rows]
+            out["per_row"] = pr
+        return out
 
     def recommend_users(self, top: int):
         """For every user (dense order): top items as (item ids, scores)."""

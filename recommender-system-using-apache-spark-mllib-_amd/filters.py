@@ -7,6 +7,8 @@ kernel takes the two conditions as
     the other side, ascending within a row, duplicates kept (Spark keeps duplicate
     ratings), and
   * one global allow set as a bitmask over the other side's dense rows.
+relevance_lists builds the same range form, de-duplicated, for the relevant sets of the
+ranking metrics (als_rank_metrics).
 Everything here is torch on whatever device the inputs live on (the tests run it on
 CPU tensors); nothing launches library code.
 """
@@ -14,7 +16,7 @@ from __future__ import annotations
 
 import torch
 
-__all__ = ["pack_allow_bits", "exclusion_lists", "reject_sharded_filters"]
+__all__ = ["pack_allow_bits", "exclusion_lists", "relevance_lists", "reject_sharded_filters"]
 
 
 def pack_allow_bits(rows: torch.Tensor, n_v: int) -> torch.Tensor:
@@ -54,6 +56,19 @@ def exclusion_lists(q_rows: torch.Tensor, o_rows: torch.Tensor, n_q: int):
     if col.numel() == 0:
         col = torch.zeros(1, dtype=torch.int32, device=q.device)
     return ptr[:-1].contiguous(), ptr[1:].contiguous(), col.contiguous()
+
+
+def relevance_lists(q_rows: torch.Tensor, o_rows: torch.Tensor, n_q: int):
+    """exclusion_lists with the (row, col) pairs de-duplicated: the relevant sets of
+    als_rank_metrics, whose ranges must be STRICTLY ascending (a relevant row counts
+    once however often the held-out data names it).  Same inputs and output form."""
+    q = q_rows.reshape(-1).long()
+    o = o_rows.reshape(-1).long()
+    if q.numel() != o.numel():
+        raise ValueError("relevant pairs: the two id arrays must have the same length")
+    ok = (q >= 0) & (q < int(n_q)) & (o >= 0)
+    key = torch.unique((q[ok] << 32) | o[ok])  # sorted, distinct
+    return exclusion_lists(key >> 32, key & 0xFFFFFFFF, n_q)
 
 
 def reject_sharded_filters(exclude, candidates) -> None:

@@ -233,6 +233,24 @@ class ALSModel:
                                 to_float32(r))
         return rm
 
+    def evaluateRanking(self, dataset, k: int, *, ratingThreshold: Optional[float] = None,
+                        exclude=None, candidates=None) -> dict:
+        """Ranking quality of each user's top-k list against the held-out rows of
+        `dataset` (userCol, itemCol; ratingCol too when ratingThreshold is given: only
+        rows with rating >= ratingThreshold are relevant): {"precision", "recall", "map",
+        "ndcg", "hitRate", "rows"} with Spark's RankingMetrics definitions at k, means
+        over the users with at least one relevant row.  exclude / candidates as
+        recommendForAllUsers (exclude="train" ranks unseen items only).  Lists and
+        metrics stay on the device (K5, K6)."""
+        p = self._p
+        cols = (p["userCol"], p["itemCol"]) + ((p["ratingCol"],) if ratingThreshold is not None
+                                               else ())
+        got = columns_of(dataset, cols)
+        return self._core.rank_metrics(
+            check_integers(got[0], p["userCol"]), check_integers(got[1], p["itemCol"]), int(k),
+            ratings=to_float32(got[2]) if ratingThreshold is not None else None,
+            threshold=ratingThreshold, **self._filters(exclude, candidates, True))
+
     # -- recommendForAll (K5) --
     def _exclude_arg(self, exclude):
         """exclude= of the recommend* methods -> the engine's form: None, "train" (the

@@ -1,0 +1,118 @@
+"""pyspark.mllib.evaluation-compatible RankingMetrics on the MI355X.
+
+``RankingMetrics(predictionAndLabels)`` takes an iterable of (predicted ids in rank
+order, relevant ids) pairs, as Spark's takes an RDD of them, and offers
+``precisionAt(k)``, ``recallAt(k)``, ``ndcgAt(k)``, ``meanAveragePrecisionAt(k)`` and
+``meanAveragePrecision`` with upstream's definitions (mllib/evaluation/
+RankingMetrics.scala, Spark 3.x, binary relevance): precision divides by k even when a
+list is shorter, the ideal DCG has min(labels, k) terms, and a row without labels
+scores 0 and still counts in the mean.
+
+The at-k metrics run on the device (kernel K6, als_rank_metrics): the lists are padded
+with -1 into one [rows, width] matrix once, the label sets become sorted ranges
+(filters.relevance_lists), and each call is one pass over the matrix.  k <= 256.
+``meanAveragePrecision`` scores whole lists of any length and divides by the number of
+labels; it is computed on the host from the same padded matrix.
+
+To score a fitted model against held-out ratings without moving its lists to the host
+at all, use ``MatrixFactorizationModel.rankingMetrics`` / ``ALSModel.evaluateRanking``.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .. import _lib
+from .. import engine as _engine
+from .. import filters as _filters
+from .._data import check_integers
+
+__all__ = ["RankingMetrics"]
+
+
+def _id_array(x, what: str) -> np.ndarray:
+    a = np.asarray(x if isinstance(x, np.ndarray) else list(x))
+    return check_integers(a.reshape(-1), what) if a.size else np.zeros(0, np.int32)
+
+
+class RankingMetrics:
+    """Evaluator for ranking algorithms (pyspark.mllib.evaluation.RankingMetrics)."""
+
+    def __init__(self, predictionAndLabels):
+        _lib.require_gpu()
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        preds, labs = [], []
+        for p, l in predictionAndLabels:
+            preds.append(_id_array(p, "prediction"))
+            labs.append(_id_array(l, "label"))
+        self.rows = n = len(preds)
+        p_len = np.array([len(p) for p in preds], np.int64)
+        l_len = np.array([len(l) for l in labs], np.int64)
+        # any int32 id -> dense non-negative value (-1 is the matrix's empty slot)
+        flat = np.concatenate(preds + labs) if n else np.zeros(0, np.int32)
+        uniq, dense = np.unique(flat, return_inverse=True)
+        dense = dense.reshape(-1).astype(np.int32)
+        n_pred = int(p_len.sum())
+        self._n_ids = max(len(uniq), 1)
+        self._width = max(int(p_len.max()) if n else 0, 1)
+        idx = np.full((n, self._width), -1, np.int32)
+        row = np.repeat(np.arange(n), p_len)
+        pos = np.arange(n_pred) - np.repeat(np.cumsum(p_len) - p_len, p_len)
+        idx[row, pos] = dense[:n_pred]
+        self._idx_host = idx
+        self._idx = torch.as_tensor(idx, device=self.device)
+        self._lab_row = np.repeat(np.arange(n), l_len)
+        self._lab_col = dense[n_pred:].astype(np.int64)
+        self._rel = _filters.relevance_lists(
+            torch.as_tensor(self._lab_row, device=self.device),
+            torch.as_tensor(self._lab_col, device=self.device), n)
+        self._ws = _engine.Workspace(self.device)
+        self._sums = {}
+
+    def _lists(self, k: int) -> torch.Tensor:
+        """The list matrix at width max(k, longest list), padded with -1."""
+        if self._idx.shape[1] < k:
+            wide = torch.full((self.rows, k), -1, dtype=torch.int32, device=self.device)
+            wide[:, :self._idx.shape[1]] = self._idx
+            self._idx = wide
+        return self._idx
+
+    def _mean(self, k, which: int) -> float:
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError(f"ranking position k should be positive, got {k!r}")
+        if k > _engine.MAX_RANK_AT:
+            raise ValueError(f"k = {k} > {_engine.MAX_RANK_AT} is not supported by the "
+                             "ranking-metrics kernel")
+        k = int(k)
+        if k not in self._sums:
+            sums, _ = _engine.rank_metrics_rows(self._lists(k), k, *self._rel, self._ws)
+            self._sums[k] = sums.tolist()
+        # rows without labels score 0 and count: the divisor is every row given
+        return self._sums[k][which] / self.rows if self.rows else float("nan")
+
+    def precisionAt(self, k: int) -> float:
+        return self._mean(k, 0)
+
+    def recallAt(self, k: int) -> float:
+        return self._mean(k, 1)
+
+    def meanAveragePrecisionAt(self, k: int) -> float:
+        return self._mean(k, 2)
+
+    def ndcgAt(self, k: int) -> float:
+        return self._mean(k, 3)
+
+    @property
+    def meanAveragePrecision(self) -> float:
+        """Mean over rows of (sum over hit positions p of hits(0..p) / (p + 1)) / labels,
+        over each whole list (Spark's meanAveragePrecision); host fp64."""
+        if not self.rows:
+            return float("nan")
+        idx = self._idx_host.astype(np.int64)
+        base = np.arange(self.rows, dtype=np.int64)[:, None] * self._n_ids
+        rel = np.unique(self._lab_row * self._n_ids + self._lab_col)
+        hit = (idx >= 0) & np.isin(base + idx, rel)
+        m = np.bincount((rel // self._n_ids), minlength=self.rows).astype(np.float64)
+        terms = np.where(hit, np.cumsum(hit, axis=1) / np.arange(1, idx.shape[1] + 1), 0.0)
+        ap = np.divide(terms.sum(axis=1), m, out=np.zeros(self.rows), where=m > 0)
+        return float(ap.sum() / self.rows)

@@ -100,6 +100,20 @@ class MatrixFactorizationModel:
         rm, _ = self._core.rmse(u, i, r)
         return rm
 
+    def rankingMetrics(self, ratings, k: int, *, threshold: Optional[float] = None,
+                       exclude=None, candidates=None) -> dict:
+        """Ranking quality of each user's top-k products against held-out (user,
+        product[, rating]) rows: {"precision", "recall", "map", "ndcg", "hitRate", "rows"}
+        with pyspark.mllib.evaluation.RankingMetrics' definitions at k, means over the
+        users with at least one relevant row (rating >= threshold when given).  exclude /
+        candidates as recommendProductsForUsers.  Lists and metrics stay on the device."""
+        if threshold is not None:
+            u, i, r = _triples(ratings)
+        else:
+            (u, i), r = _pairs(ratings), None
+        return self._core.rank_metrics(u, i, int(k), ratings=r, threshold=threshold,
+                                       **self._filters(exclude, candidates, True))
+
     def userFeatures(self):
         ids, F = self._core.user_factors()
         F = F.double().cpu().numpy()
