@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define ALS_ABI_VERSION 8
+#define ALS_ABI_VERSION 9
 
 #define ALS_OK 0
 #define ALS_EINVAL (-1)   /* bad argument (shape, null pointer, rank) */
@@ -277,6 +277,49 @@ int als_rank_metrics(const int32_t* idx, int64_t n_q, int32_t idx_ld, int32_t at
                      const int64_t* rel_begin, const int64_t* rel_end, const int32_t* rel_col,
                      double* sums_out, double* per_row_out,
                      void* ws, size_t ws_bytes, void* stream);
+
+/* ---- K7: fold-in (one row of Spark's computeFactors + CholeskySolver.solve for rows
+ *      that are not in the model; the reference serves a new user by retraining on
+ *      their ratings, RecommenderSystem.py:211-218) ------------------------------ */
+
+/* Factor rows for n_rows new rows against the fixed factor table Y_src (ABI 9): one launch,
+ * no schedule, no host sync and no pass over Y_src.
+ * Row r's ratings are col[row_ptr[r] .. row_ptr[r+1]) / val[...], dense rows of Y_src in
+ * any order; duplicates are kept, each occurrence its own term (as Spark does).  An entry
+ * with col < 0 or col >= n_src is an item the model does not know: it is skipped and not
+ * counted.  With n the number of used entries and n+ those with r > 0,
+ *   explicit:  A = sum y y^T + reg*n*I,               b = sum r y
+ *   implicit:  A = YtY + sum c1 y y^T + reg*n+*I,     b = sum_{r>0} (1+c1) y,  c1 = alpha*|r|
+ * (the arithmetic of als_solve_half and oracle/als_oracle.py normal_equations + solve);
+ * yty_packed is the lower-packed fp64 k_pad Gram als_yty writes, required iff implicit.
+ * The sums run in fp64 over the fp32 factors, ratings in row order; A is factored
+ * (square-root-free LDL^T, the solution of Spark's dppsv) and solved in fp64, and
+ * X_out[r*ld_out ..] gets the fp32 solution in columns [0, k) and zeros in [k, ld_out).
+ * Two calls give bit-identical output.  n_used_out (nullable): n_used_out[r] = n, the used
+ * entries of row r whatever their sign, in both modes.  Columns [k, ld) of Y_src are
+ * ignored: whatever they hold, NaN included, never reaches a result (the rule of K4).
+ * A row with no used entry is written as all zeros with n_used_out[r] = 0; it is not an
+ * error.  A row with a pivot that is not positive (explicit, reg = 0, fewer ratings than k,
+ * for example) sets *status_dev to row+1 if the word is still 0 — ANY ONE failing row of
+ * the call, whichever reaches the word first, not necessarily the lowest — and is written
+ * as zeros; the other rows are solved as usual.  The caller zeroes status_dev.  Positive
+ * means above 2^-46 of that pivot's diagonal entry of A: a smaller one is rounding residue
+ * of the fp64 elimination (128 * 2^-53), whose sign is chance, so a rank-deficient A is
+ * reported whichever way it rounded (dppsv, testing > 0 alone, would solve some of them).
+ * 1 <= k <= 128 (ALS_EUNSUPPORTED outside); ld, ld_out >= k and multiples of 4; Y_src and
+ * X_out 16-byte aligned; n_rows < 2^31 - 1, n_src < 2^31.  Null pointers, reg < 0,
+ * alpha < 0, implicit without yty_packed and n_rows < 0 are ALS_EINVAL, checked on the
+ * host before any device call; n_rows == 0 is a no-op returning 0.  Everything lives in
+ * registers and LDS: als_fold_in_workspace_bytes returns 0 and ws may be NULL (the two
+ * parameters are kept for uniformity with the other entry points).
+ * Parity bar: 1e-4 relative per row against the fp64 oracle; measured maxima (ranks
+ * 1-128, both modes) are in DESIGN.md section K7 and tests/test_gpu_fold_in.py. */
+size_t als_fold_in_workspace_bytes(int64_t n_rows, int32_t k);
+int als_fold_in(const int64_t* row_ptr, const int32_t* col, const float* val, int64_t n_rows,
+                const float* Y_src, int64_t n_src, int32_t ld, int32_t k,
+                float reg, int implicit, float alpha, const double* yty_packed,
+                float* X_out, int32_t ld_out, int32_t* n_used_out, int32_t* status_dev,
+                void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -74,9 +74,12 @@ SIGNATURES = {
                                          P]),
     "als_rank_metrics_workspace_bytes": (SZ, [I64]),
     "als_rank_metrics": (ctypes.c_int, [P, I64, I32, I32, P, P, P, P, P, P, SZ, P]),
+    "als_fold_in_workspace_bytes": (SZ, [I64, I32]),
+    "als_fold_in": (ctypes.c_int, [P, P, P, I64, P, I64, I32, I32, F32, ctypes.c_int, F32, P, P,
+                                   I32, P, P, P, SZ, P]),
 }
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 class ALSNativeError(RuntimeError):

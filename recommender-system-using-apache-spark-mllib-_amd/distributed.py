@@ -44,7 +44,7 @@ import torch
 import torch.distributed as dist
 
 from .engine import id_offset
-from .filters import reject_sharded_filters
+from .filters import reject_sharded_filters, reject_sharded_fold_in
 
 
 class HipKernels:
@@ -938,6 +938,16 @@ class ShardedALS:
             "rank_metrics is not supported by the sharded engine (ShardedALS) yet: evaluate "
             "rankings on a single-GPU ALSCore (e.g. ALSCore.from_factors over the gathered "
             "factors)")
+
+    def fold_in(self, ids, other_ids, ratings, *, reg, implicit=False, alpha=1.0,
+                user_side: bool = True):
+        """ALSCore.fold_in is not offered on the sharded engine yet."""
+        reject_sharded_fold_in()
+
+    def recommend_new(self, ids, other_ids, ratings, top: int, *, reg, implicit=False, alpha=1.0,
+                      user_side: bool = True, exclude_rated: bool = True, candidates=None):
+        """ALSCore.recommend_new is not offered on the sharded engine yet."""
+        reject_sharded_fold_in()
 
     def recommend_users(self, top: int):
         _, ids, sc = self.recommend_all(top, True)

@@ -404,6 +404,28 @@ def solve_half_split(block: RatingBlock, sched: SplitSchedule, part: str, Y: tor
                            w.numel(), int(ph), stream_ptr(X.device)), "als_solve_half (split)")
 
 
+def fold_in_rows(row_ptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, Y: torch.Tensor,
+                 n_src: int, rank: int, reg: float, implicit: bool, alpha: float,
+                 yty: Optional[torch.Tensor], status: torch.Tensor, ws: Workspace):
+    """K7 (als_fold_in): the factor row of every ragged row (row_ptr int64 [n + 1], col int32
+    = dense rows of Y or -1, val f32: filters.ragged_rows) against the first n_src rows of
+    the fixed factors Y, in one launch.  Returns (X f32 [n, ld_for(rank)], n_used int32
+    [n]); a row without a used entry is zero.  status: device int32, row + 1 of a row whose
+    normal equations were not positive definite (raise_status)."""
+    L = _lib.lib()
+    n = int(row_ptr.numel()) - 1
+    dev = Y.device
+    X = torch.empty((n, ld_for(rank)), dtype=torch.float32, device=dev)
+    n_used = torch.empty(n, dtype=torch.int32, device=dev)
+    need = int(L.als_fold_in_workspace_bytes(n, rank))
+    w = ws.get(need) if need else None
+    check(L.als_fold_in(ptr(row_ptr), ptr(col), ptr(val), n, ptr(Y), int(n_src), Y.shape[1],
+                        rank, float(reg), int(bool(implicit)), float(alpha), ptr(yty), ptr(X),
+                        X.shape[1], ptr(n_used), ptr(status), ptr(w), w.numel() if need else 0,
+                        stream_ptr(dev)), "als_fold_in")
+    return X, n_used
+
+
 def raise_status(s: int, where: str = "") -> None:
     """Raise for a non-zero solve status word: row + 1 of a failed Cholesky (Spark's
     dppsv info > 0), or -1 when the fp64 rescue list overflowed (als_solve_half's
@@ -830,6 +852,81 @@ class ALSCore:
                 torch.empty((0, t), dtype=torch.float32, device=self.device)
         Qs = Q.index_select(0, rows.long()).contiguous()
         idx, sc = self._topk(Qs, keys.numel(), user_side, top, exclude, candidates, rows.long())
+        return keys, ids_of(oi.ids(), idx[:, :t]), sc[:, :t]
+
+    # ---- K7: rows the model has never seen ----
+    def _fold_in(self, ids, other_ids, ratings, reg, implicit, alpha, user_side):
+        """(keys, X [m, ld], n_used, row_ptr, col) of fold_in, X with its padding columns."""
+        if self.U is None or self.V is None:
+            raise ValueError("fold_in needs factors: fit() the core or build it from_factors")
+        if reg < 0 or alpha < 0:
+            raise ValueError(f"reg and alpha must be >= 0, got {reg}, {alpha}")
+        _, _, oi, Y = self._sides(user_side)
+        q = _to_device(ids, torch.int32, self.device)
+        o = _to_device(other_ids, torch.int32, self.device)
+        r = _to_device(ratings, torch.float32, self.device)
+        keys, row_ptr, col, val = _filters.ragged_rows(q, oi.rows_of(o), r)
+        if keys.numel() == 0:
+            return (keys, torch.empty((0, ld_for(self.rank)), dtype=torch.float32,
+                                      device=self.device),
+                    torch.empty(0, dtype=torch.int32, device=self.device), row_ptr, col)
+        yty = compute_yty(Y, oi.n, self.rank, self.ws_yty) if implicit else None
+        status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        X, n_used = fold_in_rows(row_ptr, col, val, Y, oi.n, self.rank, reg, implicit, alpha, yty,
+                                 status, self.ws)
+        raise_status(int(status.item()), " of the rows folded in (distinct ids ascending)")
+        return keys, X, n_used, row_ptr, col
+
+    def fold_in(self, ids, other_ids, ratings, *, reg, implicit=False, alpha=1.0,
+                user_side: bool = True):
+        """Factor rows for rows the model was not fitted on, without a refit: one row of one
+        half-sweep each (K7, als_fold_in), x = (sum y y^T + reg n I)^-1 sum r y over the
+        row's ratings against the fixed other side (the implicit form with YtY when
+        `implicit`).  ids: the grouping key of each rating — new users (new items when
+        user_side is False); they may or may not collide with ids the model knows, and the
+        model's own U / V are never touched.  other_ids: the rated items (users); one the
+        model does not know is skipped.  reg / implicit / alpha as in fit().
+        Returns (keys [m] = the distinct ids ascending, X f32 [m, rank], n_used int32 [m] =
+        ratings used per row) on the device; a row whose every rating was skipped is zero
+        with n_used 0.  Works on a from_factors core.  Raises RuntimeError when a row's
+        normal equations are not positive definite (reg = 0 with fewer ratings than rank)."""
+        keys, X, n_used, _, _ = self._fold_in(ids, other_ids, ratings, float(reg), bool(implicit),
+                                              float(alpha), bool(user_side))
+        return keys, X[:, :self.rank], n_used
+
+    def recommend_new(self, ids, other_ids, ratings, top: int, *, reg, implicit=False, alpha=1.0,
+                      user_side: bool = True, exclude_rated: bool = True, candidates=None):
+        """fold_in, then the `top` best rows of the other side for each folded row (K5 with
+        the folded rows as the query matrix): (keys [m], ids [m, t], scores [m, t]) as
+        recommend_subset returns them, t = min(top, rows of the other side).
+        exclude_rated: a new row never lists what it rated itself (the reference's R:229
+        for a user who is not in the model); candidates: ids of the other side the lists
+        are restricted to (R:245).  Rows without a single used rating are dropped."""
+        keys, X, n_used, row_ptr, col = self._fold_in(ids, other_ids, ratings, float(reg),
+                                                      bool(implicit), float(alpha),
+                                                      bool(user_side))
+        _, _, oi, Vo = self._sides(user_side)
+        t = min(int(top), oi.n)
+        keep = n_used > 0
+        keys, Q = keys[keep], X[keep].contiguous()
+        m = int(keys.numel())
+        if m == 0:
+            return keys, torch.empty((0, t), dtype=torch.int32, device=self.device), \
+                torch.empty((0, t), dtype=torch.float32, device=self.device)
+        beg = end = ex = bits = None
+        if exclude_rated:
+            n_all = int(row_ptr.numel()) - 1
+            new_row = torch.repeat_interleave(torch.arange(n_all, device=self.device),
+                                              row_ptr[1:] - row_ptr[:-1])
+            beg, end, ex = _filters.exclusion_lists(new_row, col, n_all)
+            beg, end = beg[keep].contiguous(), end[keep].contiguous()
+        if candidates is not None:
+            c = _to_device(candidates, torch.int32, self.device)
+            bits = _filters.pack_allow_bits(oi.rows_of(c), oi.n)
+        if beg is None and bits is None:
+            idx, sc = topk_rows(Q, m, Vo, oi.n, self.rank, top)
+        else:
+            idx, sc = topk_rows_filtered(Q, m, Vo, oi.n, self.rank, top, beg, end, ex, bits)
         return keys, ids_of(oi.ids(), idx[:, :t]), sc[:, :t]
 
     def rank_metrics(self, users, items, at: int, *, ratings=None, threshold=None,

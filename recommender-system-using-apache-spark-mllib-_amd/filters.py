@@ -8,7 +8,8 @@ kernel takes the two conditions as
     ratings), and
   * one global allow set as a bitmask over the other side's dense rows.
 relevance_lists builds the same range form, de-duplicated, for the relevant sets of the
-ranking metrics (als_rank_metrics).
+ranking metrics (als_rank_metrics), and ragged_rows groups the ratings of new rows by
+their key for the fold-in (als_fold_in).
 Everything here is torch on whatever device the inputs live on (the tests run it on
 CPU tensors); nothing launches library code.
 """
@@ -16,7 +17,8 @@ from __future__ import annotations
 
 import torch
 
-__all__ = ["pack_allow_bits", "exclusion_lists", "relevance_lists", "reject_sharded_filters"]
+__all__ = ["pack_allow_bits", "exclusion_lists", "relevance_lists", "ragged_rows",
+           "reject_sharded_filters", "reject_sharded_fold_in"]
 
 
 def pack_allow_bits(rows: torch.Tensor, n_v: int) -> torch.Tensor:
@@ -69,6 +71,36 @@ def relevance_lists(q_rows: torch.Tensor, o_rows: torch.Tensor, n_q: int):
     ok = (q >= 0) & (q < int(n_q)) & (o >= 0)
     key = torch.unique((q[ok] << 32) | o[ok])  # sorted, distinct
     return exclusion_lists(key >> 32, key & 0xFFFFFFFF, n_q)
+
+
+def ragged_rows(q_keys: torch.Tensor, o_rows: torch.Tensor, vals: torch.Tensor):
+    """Ratings of new rows, (grouping key, other-side dense row, rating) per entry ->
+    (keys [m], row_ptr int64 [m + 1], col int32 [n], val f32 [n]): the distinct keys
+    ascending, and row r's entries col/val[row_ptr[r]:row_ptr[r + 1]] in input order (one
+    stable sort by key; duplicates kept, as Spark keeps duplicate ratings).  Nothing is
+    dropped: a -1 in o_rows (an id the model does not know) stays for als_fold_in to
+    skip.  Empty input gives m = 0 and row_ptr = [0].  Nothing is read back to the host
+    here beyond what torch needs to size the key list."""
+    q = q_keys.reshape(-1)
+    o = o_rows.reshape(-1)
+    v = vals.reshape(-1)
+    if not (q.numel() == o.numel() == v.numel()):
+        raise ValueError("fold-in: ids, other ids and ratings must have the same length")
+    qs, order = torch.sort(q, stable=True)
+    keys, counts = torch.unique_consecutive(qs, return_counts=True)
+    row_ptr = torch.zeros(keys.numel() + 1, dtype=torch.int64, device=q.device)
+    row_ptr[1:] = torch.cumsum(counts, 0)
+    return (keys, row_ptr, o[order].to(torch.int32).contiguous(),
+            v[order].to(torch.float32).contiguous())
+
+
+def reject_sharded_fold_in() -> None:
+    """The sharded engine carries fold_in / recommend_new with the single-GPU signature
+    and refuses them, as it refuses the filters."""
+    raise NotImplementedError(
+        "fold_in / recommend_new are not supported by the sharded engine (ShardedALS) yet: "
+        "fold new rows in on a single-GPU ALSCore (e.g. ALSCore.from_factors over the "
+        "gathered factors)")
 
 
 def reject_sharded_filters(exclude, candidates) -> None:

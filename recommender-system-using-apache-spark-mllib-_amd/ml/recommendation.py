@@ -314,6 +314,48 @@ class ALSModel:
         return self._recs_df(col, *self._core.recommend_subset(
             ids, int(numItems), True, **self._filters(exclude, candidates, True)))
 
+    # -- fold-in (K7): users / items the model was not fitted on --
+    def _fold_args(self, dataset, user_side: bool):
+        """(grouping ids, other-side ids, ratings) of `dataset` (userCol, itemCol,
+        ratingCol) and the model's own regParam / implicitPrefs / alpha."""
+        p = self._p
+        u, i, r = columns_of(dataset, (p["userCol"], p["itemCol"], p["ratingCol"]))
+        u = check_integers(u, p["userCol"])
+        i = check_integers(i, p["itemCol"])
+        a, b = (u, i) if user_side else (i, u)
+        return (a, b, to_float32(r)), dict(reg=float(p["regParam"]),
+                                           implicit=bool(p["implicitPrefs"]),
+                                           alpha=float(p["alpha"]), user_side=user_side)
+
+    def _fold_in_df(self, dataset, user_side: bool):
+        args, kw = self._fold_args(dataset, user_side)
+        keys, X, _ = self._core.fold_in(*args, **kw)
+        return self._factors_df(keys, X)
+
+    def foldInUsers(self, dataset):
+        """Factors for users that are not in the model, from their ratings alone and
+        without a refit: DataFrame[id, features], one row per distinct user of `dataset`
+        (userCol, itemCol, ratingCol), each solved against the fixed item factors with
+        the model's regParam / implicitPrefs / alpha — one row of one ALS half-sweep.
+        Items the model does not know are skipped; the model itself is not changed."""
+        return self._fold_in_df(dataset, True)
+
+    def foldInItems(self, dataset):
+        """foldInUsers for new items against the fixed user factors."""
+        return self._fold_in_df(dataset, False)
+
+    def recommendForNewUsers(self, dataset, numItems: int, *, excludeRated: bool = True,
+                             candidates=None):
+        """Top items for users that are not in the model (foldInUsers, then K5 over the
+        folded rows), in recommendForUserSubset's form.  excludeRated: a user's own rated
+        items are left out of their list; candidates: item ids the lists are restricted
+        to.  Users without a single rating of a known item are absent."""
+        args, kw = self._fold_args(dataset, True)
+        if candidates is not None:
+            candidates = check_integers(np.asarray(candidates).reshape(-1), self._p["itemCol"])
+        return self._recs_df(self._p["userCol"], *self._core.recommend_new(
+            *args, int(numItems), exclude_rated=bool(excludeRated), candidates=candidates, **kw))
+
     def recommendForItemSubset(self, dataset, numUsers: int, *, exclude=None, candidates=None):
         col = self._p["itemCol"]
         ids = check_integers(columns_of(dataset, (col,))[0], col)

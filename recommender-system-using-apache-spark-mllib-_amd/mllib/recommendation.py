@@ -162,6 +162,40 @@ class MatrixFactorizationModel:
                           if np.isfinite(s)])
                 for k, ri, rs in zip(keys, ids, sc)]
 
+    def foldInUsers(self, ratings, lambda_: float, *, implicit: bool = False,
+                    alpha: float = 0.01):
+        """Factors for users that are not in the model, from their (user, product,
+        rating) triples alone and without a refit: [(user, array)] in ascending user
+        order, each solved against the fixed product factors (one row of one ALS
+        half-sweep, K7).  lambda_ (and implicit / alpha, as in trainImplicit) are
+        arguments because this model stores no training parameters.  Products the model
+        does not know are skipped; the model itself is not changed."""
+        _check(self.rank, 0, lambda_, False, alpha)
+        u, i, r = _triples(ratings)
+        keys, X, _ = self._core.fold_in(u, i, r, reg=float(lambda_), implicit=bool(implicit),
+                                        alpha=float(alpha))
+        X = X.double().cpu().numpy()
+        return [(int(a), row) for a, row in zip(keys.cpu().numpy(), X)]
+
+    def recommendProductsForNewUsers(self, ratings, num: int, lambda_: float, *,
+                                     implicit: bool = False, alpha: float = 0.01,
+                                     exclude_rated: bool = True, candidates=None):
+        """Top `num` products for users that are not in the model (foldInUsers, then K5):
+        [(user, [Rating])] as recommendProductsForUsers returns.  exclude_rated: a user's
+        own rated products are left out; candidates: product ids the lists are restricted
+        to.  Users without a single rating of a known product are absent."""
+        _check(self.rank, 0, lambda_, False, alpha)
+        u, i, r = _triples(ratings)
+        if candidates is not None:
+            candidates = check_integers(np.asarray(candidates).reshape(-1), "product")
+        keys, ids, sc = self._core.recommend_new(
+            u, i, r, int(num), reg=float(lambda_), implicit=bool(implicit), alpha=float(alpha),
+            exclude_rated=bool(exclude_rated), candidates=candidates)
+        keys, ids, sc = keys.cpu().numpy(), ids.cpu().numpy(), sc.cpu().numpy()
+        return [(int(k), [Rating(int(k), int(a), float(s)) for a, s in zip(ri, rs)
+                          if np.isfinite(s)])
+                for k, ri, rs in zip(keys, ids, sc)]
+
     def save(self, sc, path: str, overwrite: bool = False) -> None:
         """MatrixFactorizationModel.save(sc, path) in Spark's layout (``sc`` is ignored)."""
         from .. import persistence

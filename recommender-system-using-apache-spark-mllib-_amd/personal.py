@@ -19,7 +19,8 @@ from typing import Dict, Iterable, List, Sequence, Tuple
 
 import numpy as np
 
-__all__ = ["movie_counts_and_averages", "personal_recommendations"]
+__all__ = ["movie_counts_and_averages", "personal_recommendations",
+           "personal_recommendations_fold_in"]
 
 
 def movie_counts_and_averages(ratings) -> Dict[int, Tuple[int, float]]:
@@ -39,6 +40,44 @@ def _engine_of(model):
     if eng is None:
         raise TypeError("expected a MatrixFactorizationModel or ALSModel")
     return eng
+
+
+def personal_recommendations_fold_in(model, rated: Iterable[Sequence], movies: Iterable[Sequence],
+                                     counts, reg: float, min_count: int = 75, num: int = 20
+                                     ) -> List[Tuple[float, str, int]]:
+    """personal_recommendations' output — (predicted rating, movie name, number of
+    ratings), highest prediction first — for a user who is NOT in the model, without the
+    retrain of R:218: the user's factor row is folded in from `rated` against the fixed
+    movie factors (K7) and the list comes from one filtered top-k (K5) whose candidates
+    are the movies of `movies` with more than `min_count` ratings (R:245), the user's own
+    rated movies excluded (R:229).
+
+    rated:  the new user's (user, movie, rating) triples (one user id throughout)
+    reg:    the lambda the model was trained with (explicit feedback, as the reference)
+    movies / counts: as personal_recommendations."""
+    rated = [(int(u), int(m), float(r)) for u, m, r, *_ in rated]
+    if len({u for u, _, _ in rated}) > 1:
+        raise ValueError("rated must hold the ratings of one user")
+    titles = {}
+    for m, t in movies:
+        titles.setdefault(int(m), str(t))
+
+    def count_of(m):
+        c = counts.get(m)
+        return None if c is None else (int(c[0]) if isinstance(c, tuple) else int(c))
+
+    cand = [m for m in titles if -(2 ** 31) <= m < 2 ** 31 and (count_of(m) or 0) > min_count]
+    if not rated or not cand:
+        return []
+    u, m, r = (np.asarray(x) for x in zip(*rated))
+    _, ids, sc = _engine_of(model).recommend_new(
+        u.astype(np.int32), m.astype(np.int32), r.astype(np.float32), int(num), reg=float(reg),
+        exclude_rated=True, candidates=np.asarray(cand, np.int32))
+    if ids.shape[0] == 0:   # none of the rated movies is known to the model
+        return []
+    ids, sc = ids.cpu().numpy()[0], sc.cpu().numpy()[0]
+    return [(float(s), titles[int(a)], count_of(int(a))) for a, s in zip(ids, sc)
+            if np.isfinite(s)]
 
 
 def personal_recommendations(model, user_id: int, rated: Iterable[Sequence],
