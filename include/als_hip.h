@@ -321,6 +321,49 @@ int als_fold_in(const int64_t* row_ptr, const int32_t* col, const float* val, in
                 float* X_out, int32_t ld_out, int32_t* n_used_out, int32_t* status_dev,
                 void* ws, size_t ws_bytes, void* stream);
 
+/* ---- K8: regression moments (replaces the MultivariateOnlineSummarizer pass behind
+ *      pyspark.ml.evaluation.RegressionEvaluator / pyspark.mllib.evaluation.
+ *      RegressionMetrics; the reference scores its rank sweep by validation RMSE and
+ *      compares test RMSE with a mean-rating baseline, RecommenderSystem.py:136-177) -- */
+
+/* Added under ABI 9 without a version bump: three new symbols, nothing existing changes, so
+ * a caller built against the earlier ABI 9 header keeps working.
+ * Everything the five regression metrics need, from one pass over n (label, prediction)
+ * rows.  out[8], fp64:
+ *   out[0] n          rows used            out[4] M2_pred    sum (p - mean_pred)^2
+ *   out[1] mean_label                      out[5] sse        sum (l - p)^2
+ *   out[2] M2_label   sum (l - mean_l)^2   out[6] sae        sum |l - p|
+ *   out[3] mean_pred                       out[7] n_dropped  rows left out (fused form)
+ * M2 is never formed as sum x^2 - (sum x)^2 / n: every 16-lane group (fused) or thread
+ * (columns) folds its rows into (n, mean, M2) one at a time, and partials are merged by
+ * Chan's rule (d = mean_b - mean_a, mean = mean_a + d n_b / n, M2 = M2_a + M2_b +
+ * d^2 n_a n_b / n; an empty partial is the identity) in a fixed order: inside a block,
+ * then by a single block over the per-block partials.  All arithmetic is fp64, there are
+ * no atomics, and two calls give bit-identical output.
+ * als_regression_moments (fused): label = r[e], prediction = the fp64 gather-dot of
+ * als_predict for (u[e], i[e]); a pair with an unknown id (outside its map, or mapped to
+ * -1) is left out and counted in n_dropped — computeError's inner join.  Arguments and
+ * their checks are those of als_rmse_partial, columns [k, ld) of U and V are ignored as
+ * K4 ignores them, and sse, n equal als_rmse_partial's sums up to summation order.
+ * als_regression_moments_cols: label[n] and pred[n] are fp64 device arrays; every row is
+ * used (n_dropped = 0).  A NaN in either column makes every error-derived value NaN
+ * (the means and M2 of that column, sse, sae) while n still counts the row, as Spark's
+ * summarizer does.  The means are accumulated relative to the column's first element
+ * (when finite), so data far from zero loses nothing in the merge.
+ * n < 0, null pointers (n > 0) and a bad k / ld are ALS_EINVAL, a short workspace is
+ * ALS_EWORKSPACE, all checked on the host before any device call.  n == 0 writes eight
+ * zeros (out may then be NULL: nothing is written) and returns 0; when every pair of the
+ * fused form is unknown, out is zeros with n_dropped = n.  One workspace size serves both
+ * forms. */
+size_t als_regression_moments_workspace_bytes(int64_t n);
+int als_regression_moments(const int32_t* u, const int32_t* i, const float* r, int64_t n,
+                           const int32_t* umap, int32_t umap_size,
+                           const int32_t* imap, int32_t imap_size,
+                           const float* U, const float* V, int32_t ld, int32_t k,
+                           double* out, void* ws, size_t ws_bytes, void* stream);
+int als_regression_moments_cols(const double* label, const double* pred, int64_t n,
+                                double* out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,9 @@ Surfaces (mirroring pyspark's module layout):
   als_mi355x.mllib.recommendation  ALS, MatrixFactorizationModel, Rating
                                                            (pyspark.mllib.recommendation,
                                                             RecommenderSystem.py:132)
+  als_mi355x.ml.evaluation         RankingEvaluator, RegressionEvaluator
+  als_mi355x.ml.tuning             ParamGridBuilder, TrainValidationSplit, CrossValidator
+  als_mi355x.mllib.evaluation      RankingMetrics, RegressionMetrics
   als_mi355x.engine                ALSCore — the device-resident engine
   als_mi355x.distributed           one-process-per-GPU sharded ALS (RCCL all-gather)
 """

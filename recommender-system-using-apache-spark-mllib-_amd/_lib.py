@@ -77,6 +77,10 @@ SIGNATURES = {
     "als_fold_in_workspace_bytes": (SZ, [I64, I32]),
     "als_fold_in": (ctypes.c_int, [P, P, P, I64, P, I64, I32, I32, F32, ctypes.c_int, F32, P, P,
                                    I32, P, P, P, SZ, P]),
+    "als_regression_moments_workspace_bytes": (SZ, [I64]),
+    "als_regression_moments": (ctypes.c_int, [P, P, P, I64, P, I32, P, I32, P, P, I32, I32, P, P,
+                                              SZ, P]),
+    "als_regression_moments_cols": (ctypes.c_int, [P, P, I64, P, P, SZ, P]),
 }
 
 ABI_VERSION = 9

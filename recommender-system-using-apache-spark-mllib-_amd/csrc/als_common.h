@@ -94,4 +94,36 @@ __device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
   return __builtin_bit_cast(double, iv);
 }
 
+
+// <U[umap[uid]], V[imap[iid]]> in fp64 over the fp32 factors, for the 16-lane group of the
+// calling lane (K4 predict / RMSE, K8 regression moments): each lane takes one float4 of
+// both rows per 64 columns, the group sums with xor-shuffles, and every lane returns the
+// sum.  uid / iid must be uniform across the group.  known = both ids inside their map and
+// mapped (>= 0); an unknown pair returns 0.  Columns [k, ld) are never read into the sum.
+__device__ __forceinline__ double pair_dot(int32_t uid, int32_t iid,
+                                          const int32_t* __restrict__ umap, int32_t usz,
+                                          const int32_t* __restrict__ imap, int32_t isz,
+                                          const float* __restrict__ U, const float* __restrict__ V,
+                                          int ld, int k, bool& known) {
+  const int g = threadIdx.x & 15;
+  int32_t ur = -1, ir = -1;
+  if (uid >= 0 && uid < usz) ur = umap[uid];
+  if (iid >= 0 && iid < isz) ir = imap[iid];
+  known = ur >= 0 && ir >= 0;
+  double s = 0.0;
+  if (known) {
+    for (int d0 = 4 * g; d0 < k; d0 += 64) {
+      const float4 a = *reinterpret_cast<const float4*>(U + (int64_t)ur * ld + d0);
+      const float4 b = *reinterpret_cast<const float4*>(V + (int64_t)ir * ld + d0);
+      s += (double)a.x * (double)b.x;
+      if (d0 + 1 < k) s += (double)a.y * (double)b.y;
+      if (d0 + 2 < k) s += (double)a.z * (double)b.z;
+      if (d0 + 3 < k) s += (double)a.w * (double)b.w;
+    }
+  }
+#pragma unroll
+  for (int msk = 8; msk >= 1; msk >>= 1) s += shfl_xor_f64(s, msk);
+  return s;
+}
+
 }  // namespace als

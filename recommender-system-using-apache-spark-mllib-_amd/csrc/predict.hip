@@ -18,32 +18,6 @@ namespace als {
 
 constexpr int kPairsPerBlock = 256;  // 16 pairs per pass x 16 passes
 
-__device__ __forceinline__ double pair_dot(int32_t uid, int32_t iid,
-                                          const int32_t* __restrict__ umap, int32_t usz,
-                                          const int32_t* __restrict__ imap, int32_t isz,
-                                          const float* __restrict__ U, const float* __restrict__ V,
-                                          int ld, int k, bool& known) {
-  const int g = threadIdx.x & 15;
-  int32_t ur = -1, ir = -1;
-  if (uid >= 0 && uid < usz) ur = umap[uid];
-  if (iid >= 0 && iid < isz) ir = imap[iid];
-  known = ur >= 0 && ir >= 0;
-  double s = 0.0;
-  if (known) {
-    for (int d0 = 4 * g; d0 < k; d0 += 64) {
-      const float4 a = *reinterpret_cast<const float4*>(U + (int64_t)ur * ld + d0);
-      const float4 b = *reinterpret_cast<const float4*>(V + (int64_t)ir * ld + d0);
-      s += (double)a.x * (double)b.x;
-      if (d0 + 1 < k) s += (double)a.y * (double)b.y;
-      if (d0 + 2 < k) s += (double)a.z * (double)b.z;
-      if (d0 + 3 < k) s += (double)a.w * (double)b.w;
-    }
-  }
-#pragma unroll
-  for (int msk = 8; msk >= 1; msk >>= 1) s += shfl_xor_f64(s, msk);
-  return s;
-}
-
 __global__ __launch_bounds__(256) void predict_kernel(const int32_t* __restrict__ u,
                                                       const int32_t* __restrict__ it, int64_t n,
                                                       const int32_t* __restrict__ umap, int32_t usz,

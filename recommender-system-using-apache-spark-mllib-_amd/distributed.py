@@ -44,7 +44,8 @@ import torch
 import torch.distributed as dist
 
 from .engine import id_offset
-from .filters import reject_sharded_filters, reject_sharded_fold_in
+from .filters import (reject_sharded_filters, reject_sharded_fold_in,
+                      reject_sharded_regression)
 
 
 class HipKernels:
@@ -948,6 +949,10 @@ class ShardedALS:
                       user_side: bool = True, exclude_rated: bool = True, candidates=None):
         """ALSCore.recommend_new is not offered on the sharded engine yet."""
         reject_sharded_fold_in()
+
+    def regression_metrics(self, users, items, ratings, through_origin: bool = False) -> dict:
+        """ALSCore.regression_metrics is not offered on the sharded engine yet."""
+        reject_sharded_regression()
 
     def recommend_users(self, top: int):
         _, ids, sc = self.recommend_all(top, True)

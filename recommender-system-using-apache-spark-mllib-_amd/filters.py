@@ -18,7 +18,7 @@ from __future__ import annotations
 import torch
 
 __all__ = ["pack_allow_bits", "exclusion_lists", "relevance_lists", "ragged_rows",
-           "reject_sharded_filters", "reject_sharded_fold_in"]
+           "reject_sharded_filters", "reject_sharded_fold_in", "reject_sharded_regression"]
 
 
 def pack_allow_bits(rows: torch.Tensor, n_v: int) -> torch.Tensor:
@@ -101,6 +101,15 @@ def reject_sharded_fold_in() -> None:
         "fold_in / recommend_new are not supported by the sharded engine (ShardedALS) yet: "
         "fold new rows in on a single-GPU ALSCore (e.g. ALSCore.from_factors over the "
         "gathered factors)")
+
+
+def reject_sharded_regression() -> None:
+    """The sharded engine carries regression_metrics with the single-GPU signature and
+    refuses it, as it refuses rank_metrics."""
+    raise NotImplementedError(
+        "regression_metrics is not supported by the sharded engine (ShardedALS) yet: use "
+        "rmse() there, or evaluate on a single-GPU ALSCore (e.g. ALSCore.from_factors over "
+        "the gathered factors)")
 
 
 def reject_sharded_filters(exclude, candidates) -> None:

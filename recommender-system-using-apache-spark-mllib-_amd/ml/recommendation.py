@@ -18,6 +18,7 @@ import torch
 
 from .. import engine as _engine
 from .._data import check_integers, columns_of, to_float32
+from .param import Param
 
 __all__ = ["ALS", "ALSModel"]
 
@@ -64,7 +65,7 @@ class _Params:
         self._p.update(kw)
 
     def getOrDefault(self, name):
-        return self._p[name]
+        return self._p[name.name if isinstance(name, Param) else name]
 
 
 def _make_accessors(cls, names):
@@ -115,23 +116,72 @@ class ALS(_Params):
         self._p["numItemBlocks"] = value
         return self
 
-    def fit(self, dataset) -> "ALSModel":
+    def copy(self, extra=None) -> "ALS":
+        """A new estimator with the same params and checkpoint directory; `extra` (a param
+        map: Param objects or names -> values) is applied to the copy."""
+        other = ALS(**self._p)
+        other._checkpoint_dir = self._checkpoint_dir
+        for key, value in self._param_map(extra).items():
+            other._p[key] = value
+        return other
+
+    @classmethod
+    def _param_map(cls, params) -> dict:
+        """A param map with its keys resolved to names; anything else is refused."""
+        if params is None:
+            return {}
+        if not isinstance(params, dict):
+            raise TypeError("params must be a param map (dict of Param or name -> value), a "
+                            f"list/tuple of them, or None; got {type(params).__name__}")
+        out = {}
+        for key, value in params.items():
+            if isinstance(key, Param):
+                if key.parent != cls.__name__ or key.name not in cls._defaults:
+                    raise ValueError(f"{key!r} is not a parameter of {cls.__name__}")
+                name = key.name
+            elif isinstance(key, str):
+                if key not in cls._defaults:
+                    raise ValueError(f"{key!r} is not a parameter of {cls.__name__}")
+                name = key
+            else:
+                raise TypeError(f"param map keys must be Param objects or names, got {key!r}")
+            out[name] = value
+        return out
+
+    def _columns(self, dataset):
+        """(users int32, items int32, ratings f32) of `dataset` by this estimator's columns."""
+        p = self._p
+        u, i, r = columns_of(dataset, (p["userCol"], p["itemCol"], p["ratingCol"]))
+        return check_integers(u, p["userCol"]), check_integers(i, p["itemCol"]), to_float32(r)
+
+    def _fit_core(self, core, checkpoints: bool = True):
+        """One fit of `core` (re-initialising its factors) with this estimator's params."""
         p = self._p
         _validate(p)
-        u, i, r = columns_of(dataset, (p["userCol"], p["itemCol"], p["ratingCol"]))
-        u = check_integers(u, p["userCol"])
-        i = check_integers(i, p["itemCol"])
-        r = to_float32(r)
         seed = _DEFAULT_SEED if p["seed"] is None else int(p["seed"])
-        core = _engine.make_engine(u, i, r)
         core.fit(int(p["rank"]), int(p["maxIter"]), float(p["regParam"]),
                  bool(p["implicitPrefs"]), float(p["alpha"]), seed=seed,
-                 checkpoint_dir=self._checkpoint_dir,
+                 checkpoint_dir=self._checkpoint_dir if checkpoints else None,
                  checkpoint_interval=int(p["checkpointInterval"]), resume="auto")
-        return ALSModel(core, dict(p))
+        return core
+
+    def fit(self, dataset, params=None):
+        """Fit on `dataset`.  params: a param map (Param objects or names -> values) applied
+        to a copy of this estimator, or a list / tuple of maps, which returns the list of
+        their models (pyspark's Estimator.fit)."""
+        if isinstance(params, (list, tuple)):
+            return [self.fit(dataset, m) for m in params]
+        if params is not None:
+            return self.copy(params).fit(dataset)
+        _validate(self._p)
+        core = _engine.make_engine(*self._columns(dataset))
+        return ALSModel(self._fit_core(core), dict(self._p))
 
 
 _make_accessors(ALS, list(_Params._defaults))
+for _name in _Params._defaults:  # ALS.rank, als.regParam, ...: the keys of a param map
+    setattr(ALS, _name, Param("ALS", _name))
+del _name
 
 
 class ALSModel:
@@ -232,6 +282,17 @@ class ALSModel:
         rm, _ = self._core.rmse(check_integers(u, p["userCol"]), check_integers(i, p["itemCol"]),
                                 to_float32(r))
         return rm
+
+    def evaluateRegression(self, dataset, ratingCol: Optional[str] = None) -> dict:
+        """Spark's RegressionMetrics of the model against the held-out rows of `dataset`
+        (userCol, itemCol, ratingCol), fused on the device (K8, no prediction column):
+        {"mse", "rmse", "mae", "r2", "var", "n", "dropped", "meanLabel", "varLabel"}.  Rows
+        whose user or item is unknown are left out and counted in "dropped" (the inner join
+        of rmse(), whatever coldStartStrategy says)."""
+        p = self._p
+        u, i, r = columns_of(dataset, (p["userCol"], p["itemCol"], ratingCol or p["ratingCol"]))
+        return self._core.regression_metrics(check_integers(u, p["userCol"]),
+                                             check_integers(i, p["itemCol"]), to_float32(r))
 
     def evaluateRanking(self, dataset, k: int, *, ratingThreshold: Optional[float] = None,
                         exclude=None, candidates=None) -> dict:

@@ -1,4 +1,4 @@
-"""pyspark.mllib.evaluation-compatible RankingMetrics on the MI355X.
+"""pyspark.mllib.evaluation-compatible RankingMetrics and RegressionMetrics on the MI355X.
 
 ``RankingMetrics(predictionAndLabels)`` takes an iterable of (predicted ids in rank
 order, relevant ids) pairs, as Spark's takes an RDD of them, and offers
@@ -16,6 +16,14 @@ labels; it is computed on the host from the same padded matrix.
 
 To score a fitted model against held-out ratings without moving its lists to the host
 at all, use ``MatrixFactorizationModel.rankingMetrics`` / ``ALSModel.evaluateRanking``.
+
+``RegressionMetrics(predictionAndObservations)`` takes an iterable of (prediction,
+observation) pairs — prediction first, as Spark's does — and offers ``explainedVariance``,
+``meanAbsoluteError``, ``meanSquaredError``, ``rootMeanSquaredError`` and ``r2`` with
+upstream's definitions (mllib/evaluation/RegressionMetrics.scala): one pass of kernel K8
+(als_regression_moments_cols) over the two fp64 columns.  For a fitted model use
+``MatrixFactorizationModel.regressionMetrics`` / ``ALSModel.evaluateRegression``, which
+form the predictions inside the same pass.
 """
 from __future__ import annotations
 
@@ -27,7 +35,7 @@ from .. import engine as _engine
 from .. import filters as _filters
 from .._data import check_integers
 
-__all__ = ["RankingMetrics"]
+__all__ = ["RankingMetrics", "RegressionMetrics"]
 
 
 def _id_array(x, what: str) -> np.ndarray:
@@ -116,3 +124,47 @@ class RankingMetrics:
         terms = np.where(hit, np.cumsum(hit, axis=1) / np.arange(1, idx.shape[1] + 1), 0.0)
         ap = np.divide(terms.sum(axis=1), m, out=np.zeros(self.rows), where=m > 0)
         return float(ap.sum() / self.rows)
+
+
+def moments_of_columns(label, pred) -> list:
+    """K8's 8 moments (engine.MOMENT_NAMES) of two host columns, uploaded as fp64."""
+    _lib.require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    lab = torch.as_tensor(np.ascontiguousarray(label, dtype=np.float64)).to(dev)
+    prd = torch.as_tensor(np.ascontiguousarray(pred, dtype=np.float64)).to(dev)
+    return _engine.regression_moments_cols(lab, prd, _engine.Workspace(dev)).tolist()
+
+
+class RegressionMetrics:
+    """Evaluator for regression (pyspark.mllib.evaluation.RegressionMetrics)."""
+
+    def __init__(self, predictionAndObservations, throughOrigin: bool = False):
+        _lib.require_gpu()
+        rows = predictionAndObservations
+        a = np.asarray(rows if isinstance(rows, np.ndarray) else list(rows), dtype=np.float64)
+        if a.size == 0:
+            a = a.reshape(0, 2)
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError("expected rows of 2 values (prediction, observation)")
+        self._m = _engine.regression_dict(moments_of_columns(a[:, 1], a[:, 0]),
+                                          bool(throughOrigin))
+
+    @property
+    def explainedVariance(self) -> float:
+        return self._m["var"]
+
+    @property
+    def meanAbsoluteError(self) -> float:
+        return self._m["mae"]
+
+    @property
+    def meanSquaredError(self) -> float:
+        return self._m["mse"]
+
+    @property
+    def rootMeanSquaredError(self) -> float:
+        return self._m["rmse"]
+
+    @property
+    def r2(self) -> float:
+        return self._m["r2"]

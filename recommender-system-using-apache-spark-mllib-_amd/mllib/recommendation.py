@@ -100,6 +100,14 @@ class MatrixFactorizationModel:
         rm, _ = self._core.rmse(u, i, r)
         return rm
 
+    def regressionMetrics(self, ratings) -> dict:
+        """pyspark.mllib.evaluation.RegressionMetrics of predictAll against held-out (user,
+        product, rating) rows, fused on the device (K8): {"mse", "rmse", "mae", "r2", "var",
+        "n", "dropped", "meanLabel", "varLabel"}.  Rows with an unknown user or product are
+        left out and counted in "dropped" (predictAll's inner join)."""
+        u, i, r = _triples(ratings)
+        return self._core.regression_metrics(u, i, r)
+
     def rankingMetrics(self, ratings, k: int, *, threshold: Optional[float] = None,
                        exclude=None, candidates=None) -> dict:
         """Ranking quality of each user's top-k products against held-out (user,
