@@ -364,6 +364,67 @@ int als_regression_moments(const int32_t* u, const int32_t* i, const float* r, i
 int als_regression_moments_cols(const double* label, const double* pred, int64_t n,
                                 double* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- K9: full-ranking positions and metrics (the expected percentile rank of Hu, Koren &
+ *      Volinsky's implicit-feedback paper, per-row AUC and reciprocal rank; Spark has no
+ *      counterpart, and the reference scores its models by RMSE alone,
+ *      RecommenderSystem.py:103-129) ------------------------------------------------- */
+
+/* Added under ABI 9 without a version bump, as K8 was: new symbols only.
+ * als_rank_positions: where each relevant (held-out) row of V sits in its query row's
+ * ordering of ALL admissible rows of V.  Q [n_q, ld], V [n_v, ld]: fp32 factor rows,
+ * 1 <= k <= 128 (ALS_EUNSUPPORTED outside), ld >= k and a multiple of 4, both 16-byte
+ * aligned, n_v < 2^31 - 1; columns [k, ld) are ignored (the rule of K4).
+ * rel_col[rel_begin[r] .. rel_end[r]): the relevant dense V rows of query row r, STRICTLY
+ * ascending, the form als_rank_metrics takes — except that the ranges of different rows
+ * must not overlap here, since every entry gets an output of its own.  ex_begin / ex_end /
+ * ex_col / allow_bits: the filter of als_topk_filtered with the same meaning (ex_col
+ * ascending within a range, duplicates allowed, ranges may alias; the three ex_* all NULL
+ * or all set; NULL allow_bits allows every row).  V row j is admissible for query row r
+ * when it is allowed, not excluded for r, and its score against r is not NaN (K5's rule:
+ * NaN scores are never keys).
+ * Outputs, aligned with rel_col: above_out[e] = admissible V rows other than rel_col[e]
+ * that score strictly higher, tied_out[e] = admissible other rows that score equal; both
+ * -1 for an entry that is itself inadmissible (outside [0, n_v), excluded, not allowed) or
+ * scores NaN.  n_adm_out[r] = admissible V rows of query row r, each counted once however
+ * often ex_col names it.
+ * Scores: the fp32 chain s = fmaf(q_d, v_d, s), d = 0 .. k-1 ascending from s = 0, for
+ * every score of the call, so |s - s*| <= k 2^-24 / (1 - k 2^-24) * sum_d |q_d v_d| against
+ * the fp64 dot product s* (inside tau = 2 k 2^-24 sum_d |q_d v_d|), and a pair scores
+ * bit-identically wherever it is computed.  above and tied are exact counts with respect
+ * to those scores (-0 equals +0).  The n_q x n_v matrix is never materialised and no
+ * workspace is used: ws may be NULL (the parameters are kept for uniformity).
+ * als_rank_positions_table: relevant entries one workgroup (32 query rows) ranks per sweep
+ * of V; rows holding more between them are swept again, inside the call.
+ *
+ * als_full_rank_metrics: the counts reduced to fp64 sums.  For query row r let N = n_adm[r],
+ * m = its entries with above >= 0 and p_j = above_j + tied_j / 2 (mid-rank, 0 = top):
+ *   percentile rank of an entry  p_j / (N - 1)               (rows with N > 1)
+ *   row AUC   1 - (sum_j p_j - m (m - 1) / 2) / (m (N - m))  (rows with N > m > 0)
+ *   row RR    1 / (1 + min_j p_j)                            (rows with m > 0)
+ * sums_out[11] = { sum w pr, sum w (both over the valid entries of rows with N > 1),
+ * sum of row-mean pr, sum row AUC, rows with an AUC, sum row RR, rows with an RR, rows with
+ * m > 0, valid entries, dropped entries (above < 0), rows with a row-mean pr }.  w: fp32
+ * weight per entry aligned with rel_col, NULL = 1.  per_row_out: NULL or n_q x 3 fp64 =
+ * row-mean pr, AUC, RR, NaN where undefined.  Fixed summation order (entries of a row by
+ * lane then a fixed tree, rows per wave in row order, waves in wave order, blocks by one
+ * final block): two calls give bit-identical output.  ws: 16-byte aligned, sized by
+ * als_full_rank_workspace_bytes.  n_q < 0 and null pointers are ALS_EINVAL, a short
+ * workspace ALS_EWORKSPACE, all checked on the host before any launch; n_q == 0 zeroes
+ * sums_out and returns 0. */
+size_t als_full_rank_workspace_bytes(int64_t n_q);
+int32_t als_rank_positions_table(void);
+int als_rank_positions(const float* Q, int64_t n_q, const float* V, int64_t n_v,
+                       int32_t ld, int32_t k,
+                       const int64_t* rel_begin, const int64_t* rel_end, const int32_t* rel_col,
+                       const int64_t* ex_begin, const int64_t* ex_end, const int32_t* ex_col,
+                       const uint32_t* allow_bits,
+                       int32_t* above_out, int32_t* tied_out, int32_t* n_adm_out,
+                       void* ws, size_t ws_bytes, void* stream);
+int als_full_rank_metrics(const int32_t* above, const int32_t* tied, const int32_t* n_adm,
+                          int64_t n_q, const int64_t* rel_begin, const int64_t* rel_end,
+                          const float* w, double* sums_out, double* per_row_out,
+                          void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,6 +81,11 @@ SIGNATURES = {
     "als_regression_moments": (ctypes.c_int, [P, P, P, I64, P, I32, P, I32, P, P, I32, I32, P, P,
                                               SZ, P]),
     "als_regression_moments_cols": (ctypes.c_int, [P, P, I64, P, P, SZ, P]),
+    "als_full_rank_workspace_bytes": (SZ, [I64]),
+    "als_rank_positions_table": (I32, []),
+    "als_rank_positions": (ctypes.c_int, [P, I64, P, I64, I32, I32, P, P, P, P, P, P, P, P, P, P,
+                                          P, SZ, P]),
+    "als_full_rank_metrics": (ctypes.c_int, [P, P, P, I64, P, P, P, P, P, P, SZ, P]),
 }
 
 ABI_VERSION = 9

@@ -45,7 +45,7 @@ import torch.distributed as dist
 
 from .engine import id_offset
 from .filters import (reject_sharded_filters, reject_sharded_fold_in,
-                      reject_sharded_regression)
+                      reject_sharded_full_rank, reject_sharded_regression)
 
 
 class HipKernels:
@@ -953,6 +953,12 @@ class ShardedALS:
     def regression_metrics(self, users, items, ratings, through_origin: bool = False) -> dict:
         """ALSCore.regression_metrics is not offered on the sharded engine yet."""
         reject_sharded_regression()
+
+    def full_rank_metrics(self, users, items, *, ratings=None, threshold=None, weighted=False,
+                          user_side=True, exclude=None, candidates=None, per_row=False,
+                          positions=False) -> dict:
+        """ALSCore.full_rank_metrics is not offered on the sharded engine yet."""
+        reject_sharded_full_rank()
 
     def recommend_users(self, top: int):
         _, ids, sc = self.recommend_all(top, True)

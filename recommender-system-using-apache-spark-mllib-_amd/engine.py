@@ -603,6 +603,72 @@ def rank_metrics_dict(sums, rows: int) -> dict:
             "ndcg": mean(sums[3]), "hitRate": mean(sums[5]), "rows": int(rows)}
 
 
+FULL_RANK_SUMS = ("sum_w_pr", "sum_w", "sum_row_pr", "sum_auc", "auc_rows", "sum_rr", "rr_rows",
+                  "rows", "pairs", "inadmissible", "pr_rows")   # als_full_rank_metrics' sums_out
+
+
+def rank_positions_table() -> int:
+    """Relevant entries one workgroup of K9 ranks per sweep of V (its LDS threshold table)."""
+    return int(_lib.lib().als_rank_positions_table())
+
+
+def rank_positions_rows(Q: torch.Tensor, n_q: int, V: torch.Tensor, n_v: int, rank: int,
+                        rel_begin, rel_end, rel_col, ex_begin=None, ex_end=None, ex_col=None,
+                        allow_bits=None):
+    """K9's sweep (als_rank_positions): for every relevant entry rel_col[e] of query row r
+    (rel_begin / rel_end / rel_col as filters.relevance_lists gives them) the admissible rows
+    of V that score strictly higher and equal, and per query row the admissible rows.  The
+    ex_* / allow_bits filter is topk_rows_filtered's.  Returns (above int32 [len(rel_col)],
+    tied int32, n_adm int32 [n_q]); above = tied = -1 for an entry that is itself
+    inadmissible or scores NaN, and for entries of rel_col no row points at."""
+    L = _lib.lib()
+    dev = Q.device
+    above = torch.full((max(int(rel_col.numel()), 1),), -1, dtype=torch.int32, device=dev)
+    tied = torch.full_like(above, -1)
+    n_adm = torch.zeros(max(int(n_q), 1), dtype=torch.int32, device=dev)
+    check(L.als_rank_positions(ptr(Q), int(n_q), ptr(V), int(n_v), Q.shape[1], int(rank),
+                               ptr(rel_begin), ptr(rel_end), ptr(rel_col), ptr(ex_begin),
+                               ptr(ex_end), ptr(ex_col), ptr(allow_bits), ptr(above), ptr(tied),
+                               ptr(n_adm), 0, 0, stream_ptr(dev)), "als_rank_positions")
+    return above[:rel_col.numel()], tied[:rel_col.numel()], n_adm[:int(n_q)]
+
+
+def full_rank_sums_rows(above, tied, n_adm, rel_begin, rel_end, ws: Workspace, weights=None,
+                        per_row: bool = False):
+    """K9's reduction (als_full_rank_metrics) of rank_positions_rows' counts: (sums f64 [11] in
+    FULL_RANK_SUMS order; per-row f64 [n_q, 3] = mean percentile rank, AUC, RR, or None)."""
+    L = _lib.lib()
+    n_q = int(n_adm.numel())
+    dev = n_adm.device
+    out = torch.empty(len(FULL_RANK_SUMS), dtype=torch.float64, device=dev)
+    rows = torch.empty((n_q, 3), dtype=torch.float64, device=dev) if per_row else None
+    w = ws.get(L.als_full_rank_workspace_bytes(n_q))
+    check(L.als_full_rank_metrics(ptr(above), ptr(tied), ptr(n_adm), n_q, ptr(rel_begin),
+                                  ptr(rel_end), ptr(weights), ptr(out), ptr(rows), ptr(w),
+                                  w.numel(), stream_ptr(dev)), "als_full_rank_metrics")
+    return out, rows
+
+
+def full_rank_dict(sums) -> dict:
+    """The full-ranking metrics from K9's sums (host list of 11, FULL_RANK_SUMS order).
+    expectedPercentileRank = sum w pr / sum w over the valid pairs (Hu, Koren & Volinsky's
+    measure when w is the held-out rating; 0.5 = random, lower is better),
+    meanPercentileRank = mean of the rows' mean percentile rank, auc / mrr = means of the
+    row AUC / reciprocal rank over the rows where each is defined.  A mean with an empty
+    denominator is NaN.  rows = query rows with a valid pair, pairs = valid pairs,
+    inadmissible = pairs left out because the filter excludes the item itself or its score
+    is NaN."""
+    s = [float(x) for x in sums]
+    if len(s) != len(FULL_RANK_SUMS):
+        raise ValueError(f"full_rank_dict: {len(FULL_RANK_SUMS)} sums expected, got {len(s)}")
+
+    def ratio(a, b):
+        return a / b if b > 0 else float("nan")
+    return {"expectedPercentileRank": ratio(s[0], s[1]), "meanPercentileRank": ratio(s[2], s[10]),
+            "auc": ratio(s[3], s[4]), "mrr": ratio(s[5], s[6]), "rows": int(s[7]),
+            "pairs": int(s[8]), "inadmissible": int(s[9])}
+
+
 # ---------------------------------------------------------------------------
 # The engine
 # ---------------------------------------------------------------------------
@@ -1045,6 +1111,84 @@ class ALSCore:
         if per_row:
             out["keys"] = qi.ids()[rows]
             out["per_row"] = pr
+        return out
+
+    def full_rank_metrics(self, users, items, *, ratings=None, threshold=None,
+                          weighted: bool = False, user_side: bool = True, exclude=None,
+                          candidates=None, per_row: bool = False,
+                          positions: bool = False) -> dict:
+        """Where the held-out (user, item) pairs sit in each user's ordering of ALL
+        admissible items (K9: one sweep of the whole score matrix, nothing cut at k): the
+        measure an implicit-feedback fit is judged by.  Pairs with an unknown id are left
+        out and counted in "dropped" (rmse's inner join); with `threshold` only pairs with
+        rating >= threshold are relevant; duplicates count once.  exclude / candidates as
+        rank_metrics: an item they rule out for a user is not part of that user's ordering
+        (exclude="train" ranks each held-out item among the unseen items only), and a
+        held-out pair they rule out itself is left out and counted in "inadmissible".
+        weighted: each pair weighs its rating in expectedPercentileRank (Hu, Koren &
+        Volinsky's sum r * rank / sum r; a duplicate pair keeps its first rating).
+        Returns full_rank_dict's keys — expectedPercentileRank, meanPercentileRank, auc, mrr,
+        rows, pairs, inadmissible — and "dropped".  Ties are counted at mid-rank.
+        per_row: also "keys" (ids of the query rows, ascending) and "per_row" (f64 [rows, 3]:
+        mean percentile rank, AUC, reciprocal rank; NaN where undefined), on the device.
+        positions: also "row" / "col" (query-row index into "keys" order and dense row of
+        the other side, per relevant pair), "above", "tied" (int32 per pair, -1 for an
+        inadmissible one) and "n_adm" (int32 per query row), on the device."""
+        if self.U is None or self.V is None:
+            raise ValueError("full_rank_metrics needs factors: fit() the core or build it "
+                             "from_factors")
+        qi, Q, oi, Vo = self._sides(user_side)
+        u = _to_device(users, torch.int32, self.device)
+        i = _to_device(items, torch.int32, self.device)
+        if u.numel() != i.numel():
+            raise ValueError("users and items must have the same length")
+        r = None
+        if threshold is not None or weighted:
+            if ratings is None:
+                raise ValueError("threshold / weighted need the held-out ratings")
+            r = _to_device(ratings, torch.float32, self.device)
+            if r.numel() != u.numel():
+                raise ValueError("users, items and ratings must have the same length")
+        q, o = (qi.rows_of(u), oi.rows_of(i)) if user_side else (qi.rows_of(i), oi.rows_of(u))
+        keep = (q >= 0) & (o >= 0)
+        dropped = int(u.numel()) - int(keep.sum().item())
+        if threshold is not None:
+            keep &= r >= float(threshold)
+        rows, inv = torch.unique(q[keep], return_inverse=True)  # ascending dense rows
+        n = int(rows.numel())
+        i32 = dict(dtype=torch.int32, device=self.device)
+        if n == 0:
+            out = full_rank_dict([0.0] * len(FULL_RANK_SUMS))
+            out["dropped"] = dropped
+            if per_row:
+                out["keys"] = qi.ids()[:0]
+                out["per_row"] = torch.empty((0, 3), dtype=torch.float64, device=self.device)
+            if positions:
+                out.update(row=torch.empty(0, **i32), col=torch.empty(0, **i32),
+                           above=torch.empty(0, **i32), tied=torch.empty(0, **i32),
+                           n_adm=torch.empty(0, **i32))
+                out.setdefault("keys", qi.ids()[:0])
+            return out
+        wts = None
+        if weighted:
+            beg, end, col, wts = _filters.relevance_lists_weighted(inv, o[keep], r[keep], n)
+        else:
+            beg, end, col = _filters.relevance_lists(inv, o[keep], n)
+        Qs = Q.index_select(0, rows).contiguous()
+        above, tied, n_adm = rank_positions_rows(
+            Qs, n, Vo, oi.n, self.rank, beg, end, col,
+            *self._filter_args(exclude, candidates, user_side, rows))
+        sums, pr = full_rank_sums_rows(above, tied, n_adm, beg, end, self.ws, wts, per_row)
+        out = full_rank_dict(sums.tolist())
+        out["dropped"] = dropped
+        if per_row or positions:
+            out["keys"] = qi.ids()[rows]
+        if per_row:
+            out["per_row"] = pr
+        if positions:
+            out["row"] = torch.repeat_interleave(torch.arange(n, **i32), end - beg)
+            out["col"] = col[:above.numel()]
+            out.update(above=above, tied=tied, n_adm=n_adm)
         return out
 
     def regression_metrics(self, users, items, ratings, through_origin: bool = False) -> dict:

@@ -18,7 +18,8 @@ from __future__ import annotations
 import torch
 
 __all__ = ["pack_allow_bits", "exclusion_lists", "relevance_lists", "ragged_rows",
-           "reject_sharded_filters", "reject_sharded_fold_in", "reject_sharded_regression"]
+           "relevance_lists_weighted", "reject_sharded_filters", "reject_sharded_fold_in",
+           "reject_sharded_regression", "reject_sharded_full_rank"]
 
 
 def pack_allow_bits(rows: torch.Tensor, n_v: int) -> torch.Tensor:
@@ -73,6 +74,28 @@ def relevance_lists(q_rows: torch.Tensor, o_rows: torch.Tensor, n_q: int):
     return exclusion_lists(key >> 32, key & 0xFFFFFFFF, n_q)
 
 
+def relevance_lists_weighted(q_rows: torch.Tensor, o_rows: torch.Tensor, vals: torch.Tensor,
+                             n_q: int):
+    """relevance_lists with a value column carried through (the weights of
+    als_full_rank_metrics): (begin, end, col, val f32 aligned with col).  A (row, col) pair
+    named more than once keeps its FIRST value in input order (one stable sort)."""
+    q = q_rows.reshape(-1).long()
+    o = o_rows.reshape(-1).long()
+    v = vals.reshape(-1)
+    if not (q.numel() == o.numel() == v.numel()):
+        raise ValueError("relevant pairs: ids and values must have the same length")
+    ok = (q >= 0) & (q < int(n_q)) & (o >= 0)
+    key, order = torch.sort((q[ok] << 32) | o[ok], stable=True)
+    v = v[ok][order].to(torch.float32)
+    first = torch.ones_like(key, dtype=torch.bool)
+    first[1:] = key[1:] != key[:-1]
+    key, v = key[first], v[first]
+    beg, end, col = exclusion_lists(key >> 32, key & 0xFFFFFFFF, n_q)
+    if v.numel() == 0:
+        v = torch.zeros(1, dtype=torch.float32, device=q.device)
+    return beg, end, col, v.contiguous()
+
+
 def ragged_rows(q_keys: torch.Tensor, o_rows: torch.Tensor, vals: torch.Tensor):
     """Ratings of new rows, (grouping key, other-side dense row, rating) per entry ->
     (keys [m], row_ptr int64 [m + 1], col int32 [n], val f32 [n]): the distinct keys
@@ -110,6 +133,15 @@ def reject_sharded_regression() -> None:
         "regression_metrics is not supported by the sharded engine (ShardedALS) yet: use "
         "rmse() there, or evaluate on a single-GPU ALSCore (e.g. ALSCore.from_factors over "
         "the gathered factors)")
+
+
+def reject_sharded_full_rank() -> None:
+    """The sharded engine carries full_rank_metrics with the single-GPU signature and
+    refuses it, as it refuses rank_metrics."""
+    raise NotImplementedError(
+        "full_rank_metrics is not supported by the sharded engine (ShardedALS) yet: evaluate "
+        "full rankings on a single-GPU ALSCore (e.g. ALSCore.from_factors over the gathered "
+        "factors)")
 
 
 def reject_sharded_filters(exclude, candidates) -> None:

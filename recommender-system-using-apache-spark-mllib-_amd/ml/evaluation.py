@@ -13,6 +13,11 @@ pass of kernel K8 (als_regression_moments_cols) gives every metric.  ``evaluateF
 dataset)`` is this project's extension for an ALSModel: the predictions are formed inside
 the same pass (als_regression_moments) and never materialised.  ``weightCol`` is not
 offered.
+
+``FullRankingEvaluator(metricName=, labelCol=, weighted=, exclude=).evaluateFused(model,
+dataset)`` is this project's evaluator for implicit-feedback fits: the expected percentile
+rank, AUC and reciprocal rank of the held-out items in each user's ordering of all items
+(kernel K9, als_rank_positions).
 """
 from __future__ import annotations
 
@@ -22,7 +27,7 @@ from .. import _lib
 from .. import engine as _engine
 from ..mllib.evaluation import RankingMetrics, moments_of_columns
 
-__all__ = ["RankingEvaluator", "RegressionEvaluator"]
+__all__ = ["RankingEvaluator", "RegressionEvaluator", "FullRankingEvaluator"]
 
 _METRICS = ("meanAveragePrecision", "meanAveragePrecisionAtK", "precisionAtK", "ndcgAtK",
             "recallAtK")
@@ -203,4 +208,88 @@ class RegressionEvaluator:
                                             through_origin=p["throughOrigin"])
         if d["dropped"] > 0 and str(mp["coldStartStrategy"]).lower() != "drop":
             return float("nan")
+        return d[p["metricName"]]
+
+
+_FULL_METRICS = ("expectedPercentileRank", "meanPercentileRank", "auc", "mrr")
+
+
+def _check_full_metric(name):
+    if name not in _FULL_METRICS:
+        raise ValueError(f"FullRankingEvaluator parameter metricName given invalid value "
+                         f"{name!r} (supported: {', '.join(_FULL_METRICS)})")
+    return name
+
+
+class FullRankingEvaluator:
+    """Evaluator over each user's ordering of ALL items (this project's extension; Spark has
+    no counterpart): expectedPercentileRank (the default; Hu, Koren & Volinsky's measure
+    for implicit feedback, 0.5 = random, lower is better), meanPercentileRank, auc, mrr —
+    ALSModel.evaluateFullRanking's keys (kernel K9).  The metric needs the model's factors,
+    not a prediction column, so evaluateFused(model, dataset) is the only way to score and
+    evaluate(dataset) raises; TrainValidationSplit / CrossValidator go through
+    evaluateFused.  labelCol is read for weighted=True only (the pairs' weights).
+    exclude: None, "train" (rank among the items the scored model was not fitted on) or a
+    dataset of (user, item) pairs."""
+
+    def __init__(self, metricName: str = "expectedPercentileRank", labelCol: str = "rating",
+                 weighted: bool = False, exclude="train"):
+        self._p = dict(metricName=_check_full_metric(metricName), labelCol=labelCol,
+                       weighted=bool(weighted), exclude=exclude)
+
+    def setMetricName(self, value):
+        self._p["metricName"] = _check_full_metric(value)
+        return self
+
+    def getMetricName(self) -> str:
+        return self._p["metricName"]
+
+    def setLabelCol(self, value):
+        self._p["labelCol"] = value
+        return self
+
+    def getLabelCol(self) -> str:
+        return self._p["labelCol"]
+
+    def setWeighted(self, value):
+        self._p["weighted"] = bool(value)
+        return self
+
+    def getWeighted(self) -> bool:
+        return self._p["weighted"]
+
+    def setExclude(self, value):
+        self._p["exclude"] = value
+        return self
+
+    def getExclude(self):
+        return self._p["exclude"]
+
+    def setParams(self, **kw):
+        for name, value in kw.items():
+            if name not in self._p:
+                raise TypeError(f"unknown parameter {name}")
+            getattr(self, "set" + name[0].upper() + name[1:])(value)
+        return self
+
+    def isLargerBetter(self) -> bool:
+        return self._p["metricName"] in ("auc", "mrr")
+
+    def evaluate(self, dataset) -> float:
+        raise TypeError("FullRankingEvaluator scores a model, not a prediction column: the "
+                        "position of an item among ALL items needs the factors; call "
+                        "evaluateFused(model, dataset)")
+
+    def evaluateFused(self, model, dataset) -> float:
+        """The metric of `model` (an ALSModel) over the held-out rows of `dataset`: the
+        model's user and item columns, and this evaluator's labelCol when weighted."""
+        from .._data import check_integers, columns_of, to_float32
+        p, mp = self._p, model._p
+        _lib.require_gpu()
+        cols = (mp["userCol"], mp["itemCol"]) + ((p["labelCol"],) if p["weighted"] else ())
+        got = columns_of(dataset, cols)
+        d = model.engine.full_rank_metrics(
+            check_integers(got[0], mp["userCol"]), check_integers(got[1], mp["itemCol"]),
+            ratings=to_float32(got[2]) if p["weighted"] else None, weighted=p["weighted"],
+            **model._filters(p["exclude"], None, True))
         return d[p["metricName"]]

@@ -312,6 +312,25 @@ class ALSModel:
             ratings=to_float32(got[2]) if ratingThreshold is not None else None,
             threshold=ratingThreshold, **self._filters(exclude, candidates, True))
 
+    def evaluateFullRanking(self, dataset, *, ratingThreshold: Optional[float] = None,
+                            weighted: bool = False, exclude=None, candidates=None) -> dict:
+        """Where the held-out rows of `dataset` (userCol, itemCol; ratingCol too for
+        ratingThreshold / weighted) sit in each user's ordering of ALL admissible items:
+        {"expectedPercentileRank" (0.5 = random, lower is better; with weighted=True the
+        rating-weighted measure of the implicit-ALS paper), "meanPercentileRank", "auc",
+        "mrr", "rows", "pairs", "inadmissible", "dropped"} — the way to judge an
+        implicitPrefs fit, whose RMSE says nothing about ranking.  exclude / candidates as
+        recommendForAllUsers (exclude="train" ranks among unseen items only).  One sweep of
+        the whole score matrix on the device (K9)."""
+        p = self._p
+        need_r = ratingThreshold is not None or weighted
+        cols = (p["userCol"], p["itemCol"]) + ((p["ratingCol"],) if need_r else ())
+        got = columns_of(dataset, cols)
+        return self._core.full_rank_metrics(
+            check_integers(got[0], p["userCol"]), check_integers(got[1], p["itemCol"]),
+            ratings=to_float32(got[2]) if need_r else None, threshold=ratingThreshold,
+            weighted=bool(weighted), **self._filters(exclude, candidates, True))
+
     # -- recommendForAll (K5) --
     def _exclude_arg(self, exclude):
         """exclude= of the recommend* methods -> the engine's form: None, "train" (the

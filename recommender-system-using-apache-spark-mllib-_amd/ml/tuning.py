@@ -110,8 +110,10 @@ def _default_seed(obj) -> int:
 
 # ---------------------------------------------------------------- fitting and scoring
 def _score(evaluator, model, validation) -> float:
-    from .evaluation import RegressionEvaluator
+    from .evaluation import FullRankingEvaluator, RegressionEvaluator
     from .recommendation import ALSModel
+    if isinstance(evaluator, FullRankingEvaluator):   # needs the model: no column form
+        return float(evaluator.evaluateFused(model, validation))
     if isinstance(evaluator, RegressionEvaluator) and isinstance(model, ALSModel):
         return float(evaluator.evaluateFused(model, validation))
     return float(evaluator.evaluate(model.transform(validation)))

@@ -122,6 +122,22 @@ class MatrixFactorizationModel:
         return self._core.rank_metrics(u, i, int(k), ratings=r, threshold=threshold,
                                        **self._filters(exclude, candidates, True))
 
+    def fullRankingMetrics(self, ratings, *, threshold: Optional[float] = None,
+                           weighted: bool = False, exclude=None, candidates=None) -> dict:
+        """Where held-out (user, product[, rating]) rows sit in each user's ordering of ALL
+        admissible products: {"expectedPercentileRank" (0.5 = random, lower is better;
+        rating-weighted with weighted=True, the measure of the implicit-ALS paper),
+        "meanPercentileRank", "auc", "mrr", "rows", "pairs", "inadmissible", "dropped"}: what
+        a trainImplicit model is judged by.  exclude / candidates as
+        recommendProductsForUsers.  One sweep of the whole score matrix on the device (K9)."""
+        if threshold is not None or weighted:
+            u, i, r = _triples(ratings)
+        else:
+            (u, i), r = _pairs(ratings), None
+        return self._core.full_rank_metrics(u, i, ratings=r, threshold=threshold,
+                                            weighted=bool(weighted),
+                                            **self._filters(exclude, candidates, True))
+
     def userFeatures(self):
         ids, F = self._core.user_factors()
         F = F.double().cpu().numpy()
