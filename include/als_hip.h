@@ -425,6 +425,57 @@ int als_full_rank_metrics(const int32_t* above, const int32_t* tied, const int32
                           const float* w, double* sums_out, double* per_row_out,
                           void* ws, size_t ws_bytes, void* stream);
 
+/* ---- K10: the training objective (the function whose row-wise minimiser als_solve_half
+ *      computes; Spark's ALS never evaluates it, and the reference judges a fit by held-out
+ *      RMSE alone, RecommenderSystem.py:103-129) --------------------------------------- */
+
+/* Added under ABI 9 without a version bump, as K8 and K9 were: new symbols only.
+ * With s = x_row . y_col in fp64 over the fp32 factors (the arithmetic of als_predict), lambda
+ * = regParam and Spark's lambda * numExplicits weighting (als_solve_half):
+ *   explicit  L = sum_obs (r - s)^2 + lambda (sum_u n_u |x_u|^2 + sum_i n_i |y_i|^2)
+ *   implicit  L = sum_all c (p - s)^2 + lambda (sum_u n+_u |x_u|^2 + sum_i n+_i |y_i|^2),
+ *             c = 1 + alpha |r|, p = [r > 0]; an unobserved pair has c = 1, p = 0
+ * n = ratings of the row, n+ = those with r > 0.  The sum over all pairs is never formed:
+ *   sum_all c (p - s)^2 = <X^T X, Y^T Y>_F + sum_obs [c (p - s)^2 - s^2].
+ *
+ * als_objective_side: one pass over one CSR side (row_ptr int64 [n_rows + 1], col = dense
+ * rows of Y, val; X [n_rows, ld] the side's own factors, Y [n_cols, ld] the other side's).
+ * out[5], fp64:
+ *   out[0] data   sum over the ratings of (r - s)^2, or of c (p - s)^2 - s^2 when implicit
+ *   out[1] scale  sum of the absolute values of those terms
+ *   out[2] reg    sum_row n_row |x_row|^2 (n+_row when implicit); NOT multiplied by lambda
+ *   out[3] n      ratings            out[4] n_positive  ratings with r > 0
+ * Y = NULL: no Y row is read and out[0] = out[1] = 0 (the other side's call for its
+ * regulariser: both sides hold the same ratings, so the data term is needed once).  A col
+ * outside [0, n_cols) adds no data term and is never dereferenced.  Work is split by
+ * ratings, als_objective_span() per block whichever rows they fall in, so one row of 10^5
+ * ratings costs per rating what a short one does.  alpha is widened to fp64 from the fp32
+ * the solver takes.  Columns [k, ld) of X and Y are ignored.
+ * als_gram_dot_f64: *out = <A^T A, B^T B>_F of two fp32 tables [n_a, ld] and [n_b, ld], the
+ * Grams formed HERE in fp64 on the matrix cores (not als_yty's fp32 sums: their ~1e-7
+ * relative error moves with the fixed side and would swamp the decrease being measured
+ * near convergence).  gram_a_out / gram_b_out: NULL, or k x k row-major fp64 receiving the
+ * two Grams.  Columns [k, ld) are masked, not assumed zero.
+ * Both: every sum is fp64, there are no atomics, per-block partials are folded in ascending
+ * block order and the partition depends on the sizes alone: two calls give bit-identical
+ * output.  1 <= k <= 128 (ALS_EUNSUPPORTED outside), ld >= k and a multiple of 4, factors
+ * 16-byte aligned, null pointers and negative sizes ALS_EINVAL, a short workspace
+ * ALS_EWORKSPACE — all checked on the host before any device call.  nnz == 0 (or, for the
+ * Grams, an empty table) writes zeros and returns 0; out may then be NULL.
+ * als_objective_workspace_bytes(nnz, n_rows, k) serves both calls for sides of at most nnz
+ * ratings and tables of at most n_rows rows. */
+size_t als_objective_workspace_bytes(int64_t nnz, int64_t n_rows, int32_t k);
+int32_t als_objective_span(void);
+int als_objective_side(const int64_t* row_ptr, const int32_t* col, const float* val,
+                       int64_t nnz, int32_t n_rows, int32_t n_cols,
+                       const float* X, const float* Y, int32_t ld, int32_t k,
+                       int implicit, float alpha, double* out,
+                       void* ws, size_t ws_bytes, void* stream);
+int als_gram_dot_f64(const float* A, int64_t n_a, const float* B, int64_t n_b,
+                     int32_t ld, int32_t k, double* out,
+                     double* gram_a_out, double* gram_b_out,
+                     void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,7 +45,8 @@ import torch.distributed as dist
 
 from .engine import id_offset
 from .filters import (reject_sharded_filters, reject_sharded_fold_in,
-                      reject_sharded_full_rank, reject_sharded_regression)
+                      reject_sharded_full_rank, reject_sharded_objective,
+                      reject_sharded_regression)
 
 
 class HipKernels:
@@ -785,10 +786,14 @@ class ShardedALS:
                                "equations are not positive definite (Spark raises from dppsv)")
 
     def fit(self, rank, max_iter, reg, implicit=False, alpha=1.0, seed=0, U0=None,
-            U0_global=None, checkpoint_dir=None, checkpoint_interval=10, resume=False):
+            U0_global=None, checkpoint_dir=None, checkpoint_interval=10, resume=False,
+            objective_every=0, tol=None):
         """ALSCore.fit's contract.  Checkpoints hold the dense global factors (written
-        by process 0, read by every rank), so a job may resume on another world size."""
+        by process 0, read by every rank), so a job may resume on another world size.
+        objective_every / tol (K10) are carried with the single-GPU signature and refused."""
         from . import checkpoint as C
+        if objective_every or tol is not None:
+            reject_sharded_objective()
         init = C.init_key(seed, U0 if U0 is not None else U0_global) if checkpoint_dir else None
         # process 0 decides and broadcasts (start, factors): every rank resumes alike
         start, Uc, Vc = C.resume_point_agreed(checkpoint_dir, resume, self, rank, reg, implicit,
@@ -959,6 +964,10 @@ class ShardedALS:
                           positions=False) -> dict:
         """ALSCore.full_rank_metrics is not offered on the sharded engine yet."""
         reject_sharded_full_rank()
+
+    def objective(self, reg, implicit=False, alpha=1.0) -> dict:
+        """ALSCore.objective is not offered on the sharded engine yet."""
+        reject_sharded_objective()
 
     def recommend_users(self, top: int):
         _, ids, sc = self.recommend_all(top, True)

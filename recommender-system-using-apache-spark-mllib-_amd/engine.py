@@ -669,6 +669,52 @@ def full_rank_dict(sums) -> dict:
             "pairs": int(s[8]), "inadmissible": int(s[9])}
 
 
+OBJECTIVE_SIDE = ("data", "scale", "reg", "n", "n_positive")   # als_objective_side's out
+
+
+def objective_span() -> int:
+    """Ratings one workgroup of K10's rating pass owns (als_objective_span)."""
+    return int(_lib.lib().als_objective_span())
+
+
+def objective_side(block: RatingBlock, X: torch.Tensor, Y: Optional[torch.Tensor], n_cols: int,
+                   rank: int, implicit: bool, alpha: float, ws: Workspace,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K10's rating pass over one CSR side (als_objective_side): f64 [5] in OBJECTIVE_SIDE
+    order — the data terms of the side's ratings against X (its rows) and Y (its columns),
+    their absolute sum, sum_row n_row |x_row|^2 (not yet times regParam) and the two counts.
+    Y None: the regulariser and the counts only.  out: a device f64 [5] to write into."""
+    L = _lib.lib()
+    if out is None:
+        out = torch.empty(len(OBJECTIVE_SIDE), dtype=torch.float64, device=X.device)
+    w = ws.get(L.als_objective_workspace_bytes(block.nnz, block.n_rows, rank))
+    check(L.als_objective_side(ptr(block.row_ptr), ptr(block.col), ptr(block.val), block.nnz,
+                               block.n_rows, int(n_cols), ptr(X), ptr(Y), X.shape[1], rank,
+                               int(bool(implicit)), float(alpha), ptr(out), ptr(w), w.numel(),
+                               stream_ptr(X.device)), "als_objective_side")
+    return out
+
+
+def gram_dot(A: torch.Tensor, n_a: int, B: torch.Tensor, n_b: int, rank: int, ws: Workspace,
+             grams: bool = False, out: Optional[torch.Tensor] = None):
+    """K10's <A^T A, B^T B>_F over the first n_a / n_b rows of two fp32 tables of one leading
+    dimension, the Grams formed in fp64 (als_gram_dot_f64): a device f64 [1]; with grams=True
+    (dot, A^T A, B^T B), the Grams f64 [rank, rank]."""
+    L = _lib.lib()
+    if A.shape[1] != B.shape[1]:
+        raise ValueError("gram_dot: the two tables must share a leading dimension")
+    dev = A.device
+    if out is None:
+        out = torch.empty(1, dtype=torch.float64, device=dev)
+    ga = torch.empty((rank, rank), dtype=torch.float64, device=dev) if grams else None
+    gb = torch.empty((rank, rank), dtype=torch.float64, device=dev) if grams else None
+    w = ws.get(L.als_objective_workspace_bytes(0, max(int(n_a), int(n_b)), rank))
+    check(L.als_gram_dot_f64(ptr(A), int(n_a), ptr(B), int(n_b), A.shape[1], rank, ptr(out),
+                             ptr(ga), ptr(gb), ptr(w), w.numel(), stream_ptr(dev)),
+          "als_gram_dot_f64")
+    return (out, ga, gb) if grams else out
+
+
 # ---------------------------------------------------------------------------
 # The engine
 # ---------------------------------------------------------------------------
@@ -722,6 +768,8 @@ class ALSCore:
         self.item_block = build_block(i, self.iidx, u, self.uidx, r, self.ws, chunk)
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._train_ex = {}  # user_side -> sorted training exclusion list (train_exclusion)
+        self.objective_history = []   # (iteration, objective) pairs of the last fit (K10)
+        self.iterations_run = 0       # where the last fit stopped
         self.U: Optional[torch.Tensor] = None
         self.V: Optional[torch.Tensor] = None
         self.rank = 0
@@ -740,6 +788,8 @@ class ALSCore:
         self._auto_chunk = False
         self.user_block = self.item_block = None
         self._train_ex = {}
+        self.objective_history = []
+        self.iterations_run = 0
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
         U = _to_device(U, torch.float32, self.device)
         V = _to_device(V, torch.float32, self.device)
@@ -829,12 +879,66 @@ class ALSCore:
     def check_status(self) -> None:
         raise_status(int(self.status.item()))
 
+    def objective(self, reg, implicit=False, alpha=1.0) -> dict:
+        """The training objective of the current factors: the function each half-sweep
+        minimises row by row (K10; Spark's lambda * numExplicits weighting, als_hip.h):
+          explicit  sum_obs (r - s)^2 + reg (sum_u n_u |x_u|^2 + sum_i n_i |y_i|^2)
+          implicit  sum_all c (p - s)^2 + reg (sum_u n+_u |x_u|^2 + sum_i n+_i |y_i|^2)
+        in fp64 over the stored fp32 factors.  Returns {"objective", "data" (implicit: the
+        all-pairs term, <U^T U, V^T V>_F plus the correction over the ratings), "reg"
+        (times reg already), "scale" (the sum of the absolute values of everything added:
+        the size rounding errors are relative to), "n", "n_positive"}.  Deterministic: two
+        calls on the same factors return the same bits.  One host sync."""
+        if self.user_block is None:
+            raise ValueError("objective needs the ratings the model was fitted on; this core "
+                             "was built from saved factors (from_factors / load) and has none")
+        if self.U is None or self.V is None:
+            raise ValueError("objective needs factors: fit() the core or init_factors() first")
+        if reg < 0 or alpha < 0:
+            raise ValueError(f"reg and alpha must be >= 0, got {reg}, {alpha}")
+        if getattr(self, "ws_obj", None) is None:
+            # a buffer of its own: the solve workspace keeps the rating scale between
+            # half-sweeps, and observing a fit must not make it re-measure anything
+            self.ws_obj = Workspace(self.device)
+        n = len(OBJECTIVE_SIDE)
+        out = torch.zeros(2 * n + 1, dtype=torch.float64, device=self.device)
+        objective_side(self.user_block, self.U, self.V, self.n_items, self.rank, implicit, alpha,
+                       self.ws_obj, out[:n])
+        objective_side(self.item_block, self.V, None, self.n_users, self.rank, implicit, alpha,
+                       self.ws_obj, out[n:2 * n])
+        if implicit:
+            gram_dot(self.U, self.n_users, self.V, self.n_items, self.rank, self.ws_obj,
+                     out=out[2 * n:])
+        v = out.tolist()
+        side_u, side_i, frob = dict(zip(OBJECTIVE_SIDE, v[:n])), dict(zip(OBJECTIVE_SIDE, v[n:])), v[2 * n]
+        data = side_u["data"] + frob
+        regv = float(reg) * (side_u["reg"] + side_i["reg"])
+        return {"objective": data + regv, "data": data, "reg": regv,
+                "scale": side_u["scale"] + abs(frob) + regv, "n": int(side_u["n"]),
+                "n_positive": int(side_u["n_positive"])}
+
     def fit(self, rank, max_iter, reg, implicit=False, alpha=1.0, seed=0, U0=None,
-            checkpoint_dir=None, checkpoint_interval=10, resume=False):
+            checkpoint_dir=None, checkpoint_interval=10, resume=False, objective_every=0,
+            tol=None):
         """max_iter ALS iterations from the seeded (or given U0) start.  checkpoint_dir:
         write U, V every checkpoint_interval iterations (checkpoint.py); resume
-        (True / "auto"): continue from the checkpoint there at its iteration."""
+        (True / "auto"): continue from the checkpoint there at its iteration.
+        objective_every = m > 0: evaluate objective() after iterations m, 2m, ... and after
+        the last one, into self.objective_history as (iteration, value) pairs (a resumed fit
+        starts its list at the first evaluated iteration after the checkpoint).  tol: stop
+        after an evaluated iteration whose decrease L_prev - L_cur <= tol * L_prev (tol
+        alone evaluates every iteration); a checkpoint due at that iteration is still
+        written.  self.iterations_run is where the fit stopped.  With both off (the default)
+        nothing is evaluated and no host sync is added."""
         from . import checkpoint as C
+        every = int(objective_every)
+        if every < 0:
+            raise ValueError(f"objective_every must be >= 0, got {objective_every}")
+        if tol is not None:
+            tol = float(tol)
+            if not tol >= 0:
+                raise ValueError(f"tol must be >= 0, got {tol}")
+            every = every or 1
         init = C.init_key(seed, U0) if checkpoint_dir else None
         start, Uc, Vc = C.resume_point(checkpoint_dir, resume, self, rank, reg, implicit, alpha,
                                        max_iter, init)
@@ -842,10 +946,22 @@ class ALSCore:
         if Vc is not None:
             self.V[:, :rank] = _to_device(Vc, torch.float32, self.device)
         self.status.zero_()
+        self.objective_history = []
+        self.iterations_run = start
+        prev = None
         for it in range(start, max_iter):
             self.iterate(reg, implicit, alpha)
+            stop = False
+            if every and ((it + 1) % every == 0 or it + 1 == max_iter):
+                cur = self.objective(reg, implicit, alpha)["objective"]
+                self.objective_history.append((it + 1, cur))
+                stop = tol is not None and prev is not None and prev - cur <= tol * prev
+                prev = cur
             C.maybe_save(checkpoint_dir, checkpoint_interval, it + 1, self, rank, reg, implicit,
                          alpha, init=init)
+            self.iterations_run = it + 1
+            if stop:
+                break
         self.check_status()
         return self
 

@@ -144,6 +144,15 @@ def reject_sharded_full_rank() -> None:
         "factors)")
 
 
+def reject_sharded_objective() -> None:
+    """The sharded engine carries objective and fit's objective_every / tol with the
+    single-GPU signature and refuses them, as it refuses rank_metrics."""
+    raise NotImplementedError(
+        "objective / objective_every= / tol= are not supported by the sharded engine "
+        "(ShardedALS) yet: evaluate the training objective on a single-GPU ALSCore built on "
+        "the same ratings")
+
+
 def reject_sharded_filters(exclude, candidates) -> None:
     """The sharded engine's recommend_all / recommend_subset accept the two keywords and
     refuse them: filtered serving runs on the single-GPU engine only so far."""

@@ -98,10 +98,29 @@ class ALS(_Params):
     def __init__(self, **kw):
         self._init_params(kw)
         self._checkpoint_dir = None
+        self._objective_every = 0
+        self._objective_tol = None
 
     def setCheckpointDir(self, path):
         """Directory for factor checkpoints (None disables)."""
         self._checkpoint_dir = None if path is None else str(path)
+        return self
+
+    def setObjectiveHistory(self, every=1, tol=None):
+        """Record the training objective (K10: the loss ALS itself minimises, on the training
+        data the engine holds) after every `every`-th iteration and after the last one, and
+        with `tol` stop the fit once an evaluated iteration lowers it by no more than
+        tol * its previous value.  every=0 and tol=None switch both off (the default: fit
+        evaluates nothing).  Not a Spark Param: it is not saved with the model nor
+        enumerated by the tuners, and copy() carries it over.  The fitted model's
+        objectiveHistory / objectiveIterations hold the values."""
+        every = int(every)
+        if every < 0:
+            raise ValueError(f"every must be >= 0, got {every}")
+        if tol is not None and not float(tol) >= 0:
+            raise ValueError(f"tol must be >= 0, got {tol}")
+        self._objective_every = every
+        self._objective_tol = None if tol is None else float(tol)
         return self
 
     def setParams(self, **kw):
@@ -117,10 +136,13 @@ class ALS(_Params):
         return self
 
     def copy(self, extra=None) -> "ALS":
-        """A new estimator with the same params and checkpoint directory; `extra` (a param
-        map: Param objects or names -> values) is applied to the copy."""
+        """A new estimator with the same params, checkpoint directory and objective-history
+        setting; `extra` (a param map: Param objects or names -> values) is applied to the
+        copy."""
         other = ALS(**self._p)
         other._checkpoint_dir = self._checkpoint_dir
+        other._objective_every = self._objective_every
+        other._objective_tol = self._objective_tol
         for key, value in self._param_map(extra).items():
             other._p[key] = value
         return other
@@ -159,10 +181,13 @@ class ALS(_Params):
         p = self._p
         _validate(p)
         seed = _DEFAULT_SEED if p["seed"] is None else int(p["seed"])
+        observe = {}
+        if self._objective_every or self._objective_tol is not None:
+            observe = dict(objective_every=self._objective_every, tol=self._objective_tol)
         core.fit(int(p["rank"]), int(p["maxIter"]), float(p["regParam"]),
                  bool(p["implicitPrefs"]), float(p["alpha"]), seed=seed,
                  checkpoint_dir=self._checkpoint_dir if checkpoints else None,
-                 checkpoint_interval=int(p["checkpointInterval"]), resume="auto")
+                 checkpoint_interval=int(p["checkpointInterval"]), resume="auto", **observe)
         return core
 
     def fit(self, dataset, params=None):
@@ -190,6 +215,8 @@ class ALSModel:
     def __init__(self, core: "_engine.ALSCore", params: dict):
         self._core = core
         self._p = params
+        # the fit's (iteration, objective) pairs, copied: a tuner refits the same core
+        self._objective_history = list(getattr(core, "objective_history", ()))
 
     # -- params used at transform time --
     def setUserCol(self, v):
@@ -222,6 +249,27 @@ class ALSModel:
     @property
     def engine(self) -> "_engine.ALSCore":
         return self._core
+
+    @property
+    def objectiveHistory(self):
+        """The training objective after each evaluated iteration of the fit (named after
+        Spark's training summaries; ALS.setObjectiveHistory switches it on).  Empty when
+        the fit recorded none and for a loaded model."""
+        return [v for _, v in self._objective_history]
+
+    @property
+    def objectiveIterations(self):
+        """The iteration number (1-based) of each entry of objectiveHistory."""
+        return [it for it, _ in self._objective_history]
+
+    def trainingObjective(self) -> dict:
+        """The objective of the model's factors on its training data, for the regParam /
+        implicitPrefs / alpha it was fitted with (K10, ALSCore.objective): {"objective",
+        "data", "reg", "scale", "n", "n_positive"}.  Raises ValueError on a loaded model,
+        which holds no training data."""
+        p = self._p
+        return self._core.objective(float(p["regParam"]), bool(p["implicitPrefs"]),
+                                    float(p["alpha"]))
 
     def _factors_df(self, ids, F):
         import pandas as pd

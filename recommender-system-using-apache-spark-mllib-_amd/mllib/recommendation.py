@@ -108,6 +108,15 @@ class MatrixFactorizationModel:
         u, i, r = _triples(ratings)
         return self._core.regression_metrics(u, i, r)
 
+    def trainingObjective(self, lambda_: float, implicit: bool = False,
+                          alpha: float = 0.01) -> dict:
+        """The objective ALS minimises, of this model's factors on the ratings it was trained
+        on (K10): {"objective", "data", "reg", "scale", "n", "n_positive"}.  lambda_ (and
+        implicit / alpha, as in trainImplicit) are arguments because this model stores no
+        training parameters.  Raises ValueError on a loaded model, which holds no ratings."""
+        _check(self.rank, 0, lambda_, False, alpha)
+        return self._core.objective(float(lambda_), bool(implicit), float(alpha))
+
     def rankingMetrics(self, ratings, k: int, *, threshold: Optional[float] = None,
                        exclude=None, candidates=None) -> dict:
         """Ranking quality of each user's top-k products against held-out (user,
