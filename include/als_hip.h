@@ -476,6 +476,49 @@ int als_gram_dot_f64(const float* A, int64_t n_a, const float* B, int64_t n_b,
                      double* gram_a_out, double* gram_b_out,
                      void* ws, size_t ws_bytes, void* stream);
 
+/* ---- K11: explain a score as one contribution per rating of the row (the follow-up of the
+ *      reference's closing top-20 print, RecommenderSystem.py:247: "because you rated X 5
+ *      and Y 4"; implicit.explain offers it, Spark does not) ---- */
+
+/* Added under ABI 9 without a version bump: two new symbols, nothing existing changes.
+ * A row's factor solves its normal equations, x = A^-1 b with b = sum_j wb_j y_j, so
+ *   score(row, t) = y_t^T A^-1 b = sum_j wb_j (z_t . y_j),   z_t = A^-1 y_t,
+ * one term per used entry j of the row.  The row's entries, the skipped ones (col < 0 or
+ * col >= n_src), duplicates, n, the weights wa / wb, the YtY term, the pivot rule and the
+ * status word are exactly als_fold_in's (above); A is formed and factored once per row, in
+ * fp64, however many targets the row has.
+ * Targets are ragged: row r explains tgt[tgt_ptr[r] .. tgt_ptr[r+1]), dense rows of Y_src;
+ * T = tgt_ptr[n_rows] slots in all, and slot s writes
+ *   score[s]                  the fp64 sum of ALL the row's contributions in row order
+ *                             (not only the listed ones), rounded to fp32
+ *   contrib[s*top_n + i]      the i-th largest contribution, fp64 rounded to fp32
+ *   contrib_pos[s*top_n + i]  the offset inside the row (0 = col[row_ptr[r]]) of the entry
+ *                             that made it
+ * ordered by fp64 contribution descending, ties by ascending offset.  Every used entry is a
+ * candidate (an implicit entry with r <= 0 has wb = 0 and contributes exactly 0); list
+ * slots past the row's used entries hold contrib_pos -1 and contrib 0.  The dot comes
+ * first, then the weight, so two entries of one item with one rating tie bit for bit.  A
+ * target the row also rated and a repeated target are ordinary.  An unknown target (< 0 or
+ * >= n_src), a row without a used entry and a row whose A is not positive definite (which
+ * sets *status_dev to row+1 as als_fold_in does) get score 0 and an empty list.  A row
+ * without targets is counted (n_used_out) but not factored and cannot set the status.
+ * n_used_out is nullable.  Two calls give bit-identical output.
+ * 1 <= k <= 128 and 1 <= top_n <= 32 (ALS_EUNSUPPORTED outside); ld >= k and a multiple of
+ * 4; Y_src 16-byte aligned; a row has fewer than 2^31 entries.  Null pointers (tgt, score,
+ * contrib_pos and contrib too, even when T is 0), reg < 0, alpha < 0, implicit without
+ * yty_packed and n_rows < 0 are ALS_EINVAL, checked on the host before any device call;
+ * n_rows == 0 is a no-op returning 0.  als_explain_workspace_bytes returns 0 and ws may be
+ * NULL.  Measured error against the fp64 reference and the cost against als_fold_in:
+ * DESIGN.md section K11. */
+size_t als_explain_workspace_bytes(int64_t n_rows, int32_t k);
+int als_explain(const int64_t* row_ptr, const int32_t* col, const float* val, int64_t n_rows,
+                const float* Y_src, int64_t n_src, int32_t ld, int32_t k,
+                float reg, int implicit, float alpha, const double* yty_packed,
+                const int64_t* tgt_ptr, const int32_t* tgt, int32_t top_n,
+                float* score, int32_t* contrib_pos, float* contrib,
+                int32_t* n_used_out, int32_t* status_dev,
+                void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

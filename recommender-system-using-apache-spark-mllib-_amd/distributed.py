@@ -44,7 +44,7 @@ import torch
 import torch.distributed as dist
 
 from .engine import id_offset
-from .filters import (reject_sharded_filters, reject_sharded_fold_in,
+from .filters import (reject_sharded_explain, reject_sharded_filters, reject_sharded_fold_in,
                       reject_sharded_full_rank, reject_sharded_objective,
                       reject_sharded_regression)
 
@@ -954,6 +954,11 @@ class ShardedALS:
                       user_side: bool = True, exclude_rated: bool = True, candidates=None):
         """ALSCore.recommend_new is not offered on the sharded engine yet."""
         reject_sharded_fold_in()
+
+    def explain(self, users, items, top_n: int = 10, *, reg, implicit=False, alpha=1.0,
+                user_side: bool = True, ratings=None):
+        """ALSCore.explain is not offered on the sharded engine yet."""
+        reject_sharded_explain()
 
     def regression_metrics(self, users, items, ratings, through_origin: bool = False) -> dict:
         """ALSCore.regression_metrics is not offered on the sharded engine yet."""

@@ -426,6 +426,53 @@ def fold_in_rows(row_ptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, Y:
     return X, n_used
 
 
+EXPLAIN_MAX_TOP = 32
+
+
+def explain_rows(row_ptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, Y: torch.Tensor,
+                 n_src: int, rank: int, reg: float, implicit: bool, alpha: float,
+                 yty: Optional[torch.Tensor], tgt_ptr: torch.Tensor, tgt: torch.Tensor,
+                 top_n: int, status: torch.Tensor, ws: Workspace):
+    """K11 (als_explain): every score of the ragged rows (fold_in_rows' inputs) against their
+    ragged targets (tgt_ptr int64 [n + 1], tgt int32 = dense rows of Y or -1, tgt_ptr[n] ==
+    tgt.numel() == T) split into one contribution per rating, in one launch.  Returns
+    (score f32 [T], contrib_pos int32 [T, top_n] = entry offset inside the row or -1,
+    contrib f32 [T, top_n] descending, n_used int32 [n]).  status as fold_in_rows."""
+    L = _lib.lib()
+    n = int(row_ptr.numel()) - 1
+    T = int(tgt.numel())
+    dev = Y.device
+    if T == 0:  # the entry point wants addresses even when no slot is written
+        tgt = torch.full((1,), -1, dtype=torch.int32, device=dev)
+    score = torch.empty(max(T, 1), dtype=torch.float32, device=dev)
+    pos = torch.empty((max(T, 1), int(top_n)), dtype=torch.int32, device=dev)
+    contrib = torch.empty((max(T, 1), int(top_n)), dtype=torch.float32, device=dev)
+    n_used = torch.empty(n, dtype=torch.int32, device=dev)
+    if col.numel() == 0:  # rows without a single entry: never read, but not null
+        col = torch.zeros(1, dtype=torch.int32, device=dev)
+        val = torch.zeros(1, dtype=torch.float32, device=dev)
+    need = int(L.als_explain_workspace_bytes(n, rank))
+    w = ws.get(need) if need else None
+    check(L.als_explain(ptr(row_ptr), ptr(col), ptr(val), n, ptr(Y), int(n_src), Y.shape[1],
+                        rank, float(reg), int(bool(implicit)), float(alpha), ptr(yty),
+                        ptr(tgt_ptr), ptr(tgt), int(top_n), ptr(score), ptr(pos), ptr(contrib),
+                        ptr(n_used), ptr(status), ptr(w), w.numel() if need else 0,
+                        stream_ptr(dev)), "als_explain")
+    return score[:T], pos[:T], contrib[:T], n_used
+
+
+def group_pairs(rows: torch.Tensor, n_rows: int):
+    """Pairs' row index (int64, in [0, n_rows)) -> (order, tgt_ptr int64 [n_rows + 1]):
+    `order` lists the pairs grouped by row (stable: input order within a row), so pair
+    order[s] fills target slot s of als_explain and each row is factored once."""
+    rows = rows.reshape(-1).long()
+    order = torch.sort(rows, stable=True).indices
+    tgt_ptr = torch.zeros(int(n_rows) + 1, dtype=torch.int64, device=rows.device)
+    if rows.numel():
+        tgt_ptr[1:] = torch.cumsum(torch.bincount(rows, minlength=int(n_rows)), 0)
+    return order, tgt_ptr
+
+
 def raise_status(s: int, where: str = "") -> None:
     """Raise for a non-zero solve status word: row + 1 of a failed Cholesky (Spark's
     dppsv info > 0), or -1 when the fp64 rescue list overflowed (als_solve_half's
@@ -1176,6 +1223,105 @@ class ALSCore:
         else:
             idx, sc = topk_rows_filtered(Q, m, Vo, oi.n, self.rank, top, beg, end, ex, bits)
         return keys, ids_of(oi.ids(), idx[:, :t]), sc[:, :t]
+
+    # ---- K11: why was this recommended? ----
+    def _explain_rows_of(self, q, user_side: bool, ratings):
+        """(pair row int64 or -1, row_ptr, col, val): the rating rows behind the query ids
+        q — slices of the training block (ratings None) or the caller's ratings grouped by
+        filters.ragged_rows."""
+        qi, _, oi, _ = self._sides(user_side)
+        if ratings is not None:
+            ids, other, vals = ratings
+            keys, row_ptr, col, val = _filters.ragged_rows(
+                _to_device(ids, torch.int32, self.device),
+                oi.rows_of(_to_device(other, torch.int32, self.device)),
+                _to_device(vals, torch.float32, self.device))
+            if keys.numel() == 0:
+                return torch.full_like(q, -1, dtype=torch.int64), row_ptr, col, val
+            at = torch.searchsorted(keys, q).clamp_(max=keys.numel() - 1)
+            return torch.where(keys[at] == q, at, -1), row_ptr, col, val
+        block = self.user_block if user_side else self.item_block
+        if block is None:
+            raise ValueError("explain needs each row's ratings; this core was built from saved "
+                             "factors (from_factors / load) and holds none: pass ratings=(ids, "
+                             "other ids, values)")
+        dense = qi.rows_of(q)
+        uniq, inv = torch.unique(dense[dense >= 0], return_inverse=True)
+        pair_row = torch.full_like(dense, -1)
+        pair_row[dense >= 0] = inv
+        beg = block.row_ptr[uniq]
+        lens = block.row_ptr[uniq + 1] - beg
+        row_ptr = torch.zeros(uniq.numel() + 1, dtype=torch.int64, device=self.device)
+        row_ptr[1:] = torch.cumsum(lens, 0)
+        src = (torch.repeat_interleave(beg - row_ptr[:-1], lens)
+               + torch.arange(int(row_ptr[-1]), device=self.device))
+        return pair_row, row_ptr, block.col[src].contiguous(), block.val[src].contiguous()
+
+    def explain(self, users, items, top_n: int = 10, *, reg, implicit=False, alpha=1.0,
+                user_side: bool = True, ratings=None):
+        """Why each (user, item) pair scores what it does: the score as a sum with one term
+        per rating the user gave, score = sum_j wb_j y_i^T A_u^-1 y_j over the user's
+        normal equations (K11, als_explain; reg / implicit / alpha as in fit(), and as in
+        fold_in they decide A_u).  Pairs are grouped by user, so a user is factored once
+        however many items are explained.
+        ratings=None: each user's ratings are the ones the core was fitted on.
+        ratings=(ids, other_ids, values): the rows to explain from, grouped by id as fold_in
+        groups them — users the model has never seen, or a core restored from_factors.
+        user_side=False explains item rows against the user factors: the row is the item,
+        its ratings are users, and the contributions name users.
+        Returns device tensors over the pairs kept, in input order (a pair whose user has no
+        rating row — unknown to the model, or absent from `ratings` — is dropped):
+        (users [m], items [m], score f32 [m], ids int32 [m, top_n], ratings f32 [m, top_n],
+        contrib f32 [m, top_n], n_contrib int32 [m]).  Row p lists its n_contrib[p] largest
+        contributions, descending (ties: earlier rating first): the id of the other side
+        that was rated, the rating, and its share of the score; slots past n_contrib hold
+        id -1, rating 0 and contribution 0.  score sums ALL the row's contributions, not
+        only the listed ones; it is NaN for a target the model does not know.  After a
+        fit, score equals predict() to rounding on the side solved last (users)."""
+        top_n = int(top_n)
+        if not 1 <= top_n <= EXPLAIN_MAX_TOP:
+            raise ValueError(f"top_n must be in [1, {EXPLAIN_MAX_TOP}], got {top_n}")
+        if self.U is None or self.V is None:
+            raise ValueError("explain needs factors: fit() the core or build it from_factors")
+        reg, alpha = float(reg), float(alpha)
+        if reg < 0 or alpha < 0:
+            raise ValueError(f"reg and alpha must be >= 0, got {reg}, {alpha}")
+        _, _, oi, Y = self._sides(user_side)
+        u = _to_device(users, torch.int32, self.device).reshape(-1)
+        i = _to_device(items, torch.int32, self.device).reshape(-1)
+        if u.numel() != i.numel():
+            raise ValueError("users and items must have the same length")
+        q, o = (u, i) if user_side else (i, u)
+        pair_row, row_ptr, col, val = self._explain_rows_of(q, bool(user_side), ratings)
+        keep = pair_row >= 0
+        u, i, o, pair_row = u[keep], i[keep], o[keep], pair_row[keep]
+        m = int(u.numel())
+        f32 = dict(dtype=torch.float32, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        if m == 0:
+            return (u, i, torch.empty(0, **f32), torch.empty((0, top_n), **i32),
+                    torch.empty((0, top_n), **f32), torch.empty((0, top_n), **f32),
+                    torch.empty(0, **i32))
+        n_rows = int(row_ptr.numel()) - 1
+        order, tgt_ptr = group_pairs(pair_row, n_rows)
+        tgt = oi.rows_of(o)[order].to(torch.int32).contiguous()
+        yty = compute_yty(Y, oi.n, self.rank, self.ws_yty) if implicit else None
+        status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        score, pos, contrib, _ = explain_rows(row_ptr, col, val, Y, oi.n, self.rank, reg,
+                                              bool(implicit), alpha, yty, tgt_ptr, tgt, top_n,
+                                              status, self.ws)
+        raise_status(int(status.item()), " of the rows explained (distinct ids ascending)")
+        # entry offset inside the row -> the rated id and its rating
+        filled = pos >= 0
+        entry = (row_ptr[pair_row[order]].unsqueeze(1) + pos.clamp(min=0).long())
+        entry = torch.where(filled, entry, 0)
+        ids = torch.where(filled, ids_of(oi.ids(), col[entry].clamp(min=0)), -1).to(torch.int32)
+        rat = torch.where(filled, val[entry], 0.0)
+        score = torch.where(tgt >= 0, score, float("nan"))
+        back = torch.empty_like(order)
+        back[order] = torch.arange(m, device=self.device)  # slot of each input pair
+        return (u, i, score[back], ids[back], rat[back], contrib[back],
+                filled.sum(1).to(torch.int32)[back])
 
     def rank_metrics(self, users, items, at: int, *, ratings=None, threshold=None,
                      user_side: bool = True, exclude=None, candidates=None,

@@ -19,7 +19,7 @@ import torch
 
 __all__ = ["pack_allow_bits", "exclusion_lists", "relevance_lists", "ragged_rows",
            "relevance_lists_weighted", "reject_sharded_filters", "reject_sharded_fold_in",
-           "reject_sharded_regression", "reject_sharded_full_rank"]
+           "reject_sharded_regression", "reject_sharded_full_rank", "reject_sharded_explain"]
 
 
 def pack_allow_bits(rows: torch.Tensor, n_v: int) -> torch.Tensor:
@@ -124,6 +124,15 @@ def reject_sharded_fold_in() -> None:
         "fold_in / recommend_new are not supported by the sharded engine (ShardedALS) yet: "
         "fold new rows in on a single-GPU ALSCore (e.g. ALSCore.from_factors over the "
         "gathered factors)")
+
+
+def reject_sharded_explain() -> None:
+    """The sharded engine carries explain with the single-GPU signature and refuses it, as
+    it refuses fold_in."""
+    raise NotImplementedError(
+        "explain is not supported by the sharded engine (ShardedALS) yet: explain scores on "
+        "a single-GPU ALSCore (e.g. ALSCore.from_factors over the gathered factors, with "
+        "ratings=)")
 
 
 def reject_sharded_regression() -> None:

@@ -484,6 +484,35 @@ class ALSModel:
         return self._recs_df(self._p["userCol"], *self._core.recommend_new(
             *args, int(numItems), exclude_rated=bool(excludeRated), candidates=candidates, **kw))
 
+    # -- explain (K11): why was this item recommended to this user? --
+    def explainRecommendations(self, dataset, numContributions: int = 10, *, ratings=None):
+        """Each (userCol, itemCol) pair of `dataset` explained by the user's own ratings:
+        DataFrame[userCol, itemCol, predictionCol, contributions], contributions a list of
+        (item, rating, contribution) — "because you rated item 4.0" — largest contribution
+        first, at most numContributions (<= 32) of them.  A prediction is the sum of one
+        term per rating of the user (over ALL of them, listed or not), exact for ALS: the
+        user's factor solves normal equations that are linear in those ratings (K11), with
+        the model's regParam / implicitPrefs / alpha.
+        ratings=None explains from the ratings the model was fitted on; a loaded model holds
+        none and needs ratings= — a dataset (userCol, itemCol, ratingCol) with the ratings
+        of the users to explain, who need not be in the model.  Pairs of users without
+        ratings are absent; an item the model does not know gives NaN and no contributions."""
+        import pandas as pd
+        p = self._p
+        u, i = columns_of(dataset, (p["userCol"], p["itemCol"]))
+        kw = dict(reg=float(p["regParam"]), implicit=bool(p["implicitPrefs"]),
+                  alpha=float(p["alpha"]))
+        if ratings is not None:
+            ratings, _ = self._fold_args(ratings, True)  # the same three conventions
+        uu, ii, sc, ids, rat, con, n = (x.cpu().numpy() for x in self._core.explain(
+            check_integers(u, p["userCol"]), check_integers(i, p["itemCol"]),
+            int(numContributions), ratings=ratings, **kw))
+        lists = [[(int(a), float(b), float(c)) for a, b, c in zip(ids[r, :n[r]], rat[r, :n[r]],
+                                                                  con[r, :n[r]])]
+                 for r in range(len(uu))]
+        return pd.DataFrame({p["userCol"]: uu, p["itemCol"]: ii, p["predictionCol"]: sc,
+                             "contributions": lists})
+
     def recommendForItemSubset(self, dataset, numUsers: int, *, exclude=None, candidates=None):
         col = self._p["itemCol"]
         ids = check_integers(columns_of(dataset, (col,))[0], col)

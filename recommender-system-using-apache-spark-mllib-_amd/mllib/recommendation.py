@@ -229,6 +229,30 @@ class MatrixFactorizationModel:
                           if np.isfinite(s)])
                 for k, ri, rs in zip(keys, ids, sc)]
 
+    def explain(self, user_product, lambda_: float, num: int = 10, *, implicit: bool = False,
+                alpha: float = 0.01, ratings=None):
+        """Each (user, product) pair explained by the user's own ratings: [(user, product,
+        score, [(product, rating, contribution), ...])], at most `num` (<= 32) contributions,
+        largest first.  score is the sum of one contribution per rating of the user (all of
+        them, listed or not): the user's factor solves normal equations that are linear in
+        those ratings (K11).  lambda_ (and implicit / alpha, as in trainImplicit) are
+        arguments because this model stores no training parameters.  ratings=None explains
+        from the ratings the model was trained on; a loaded model holds none and needs
+        ratings= — (user, product, rating) triples of the users to explain, who need not be
+        in the model.  Pairs of users without ratings are absent; a product the model does
+        not know gives NaN and no contributions."""
+        _check(self.rank, 0, lambda_, False, alpha)
+        u, i = _pairs(user_product)
+        if ratings is not None:
+            ratings = _triples(ratings)
+        uu, ii, sc, ids, rat, con, n = (x.cpu().numpy() for x in self._core.explain(
+            u, i, int(num), reg=float(lambda_), implicit=bool(implicit), alpha=float(alpha),
+            ratings=ratings))
+        return [(int(uu[r]), int(ii[r]), float(sc[r]),
+                 [(int(a), float(b), float(c))
+                  for a, b, c in zip(ids[r, :n[r]], rat[r, :n[r]], con[r, :n[r]])])
+                for r in range(len(uu))]
+
     def save(self, sc, path: str, overwrite: bool = False) -> None:
         """MatrixFactorizationModel.save(sc, path) in Spark's layout (``sc`` is ignored)."""
         from .. import persistence

@@ -20,7 +20,7 @@ from typing import Dict, Iterable, List, Sequence, Tuple
 import numpy as np
 
 __all__ = ["movie_counts_and_averages", "personal_recommendations",
-           "personal_recommendations_fold_in"]
+           "personal_recommendations_fold_in", "personal_explanations"]
 
 
 def movie_counts_and_averages(ratings) -> Dict[int, Tuple[int, float]]:
@@ -78,6 +78,40 @@ def personal_recommendations_fold_in(model, rated: Iterable[Sequence], movies: I
     ids, sc = ids.cpu().numpy()[0], sc.cpu().numpy()[0]
     return [(float(s), titles[int(a)], count_of(int(a))) for a, s in zip(ids, sc)
             if np.isfinite(s)]
+
+
+def personal_explanations(model, rated: Iterable[Sequence], movies: Iterable[Sequence],
+                          movie_ids: Iterable[int], reg: float, num: int = 10
+                          ) -> List[Tuple[str, float, List[Tuple[str, float, float]]]]:
+    """Why the fold-in person of personal_recommendations_fold_in is recommended what they
+    are: for each movie of `movie_ids` the model knows, (movie name, predicted rating,
+    [(rated movie name, the rating given, its contribution to the prediction), ...]), the
+    `num` largest contributions first — "because you rated X 5 and Y 4".  The prediction is
+    the one the fold-in serves (the same normal equations, K11) and is the sum of one
+    contribution per rating in `rated`, listed or not.
+
+    rated:  the person's (user, movie, rating) triples (one user id throughout)
+    movies: (MovieID, title) pairs; a movie without a title is named by its id
+    reg:    the lambda the model was trained with (explicit feedback, as the reference)."""
+    rated = [(int(u), int(m), float(r)) for u, m, r, *_ in rated]
+    if len({u for u, _, _ in rated}) > 1:
+        raise ValueError("rated must hold the ratings of one user")
+    titles = {}
+    for m, t in movies:
+        titles.setdefault(int(m), str(t))
+    want = [int(m) for m in movie_ids if -(2 ** 31) <= int(m) < 2 ** 31]
+    if not rated or not want:
+        return []
+    u, m, r = (np.asarray(x) for x in zip(*rated))
+    ratings = (u.astype(np.int32), m.astype(np.int32), r.astype(np.float32))
+    _, ii, sc, ids, rat, con, n = (x.cpu().numpy() for x in _engine_of(model).explain(
+        np.full(len(want), u[0], np.int32), np.asarray(want, np.int32), int(num), reg=float(reg),
+        ratings=ratings))
+    name = lambda a: titles.get(int(a), str(int(a)))
+    return [(name(ii[p]), float(sc[p]),
+             [(name(a), float(b), float(c))
+              for a, b, c in zip(ids[p, :n[p]], rat[p, :n[p]], con[p, :n[p]])])
+            for p in range(len(ii)) if not np.isnan(sc[p])]
 
 
 def personal_recommendations(model, user_id: int, rated: Iterable[Sequence],
