@@ -41,6 +41,7 @@
 //  * YtY (K2b): 512-row tasks of the same MFMA Gram, fp64 slots, parallel slot
 //    sum, fixed order.
 #include "als_common.h"
+#include "task_order.h"
 
 #include <algorithm>
 #include <utility>
@@ -839,7 +840,9 @@ __global__ __launch_bounds__(256) void split_table_kernel(const float* __restric
 
 // Launch-1 task t -> heavy-row chunk or light row: the two lists interleaved
 // while both last (memory-bound Gram-only chunks beside VALU-heavy fused
-// solves), each in its own LPT order.
+// solves), each in its own LPT order.  (The implicit and W1 launches; the rank
+// 33-64 explicit launch spreads the chunks through the light list instead:
+// decode_task_merged, task_order.h.)
 __device__ __forceinline__ void decode_task(int t, int n_chunks, int n_light, int& chunk,
                                             int& light) {
   const int P = n_chunks < n_light ? n_chunks : n_light;
@@ -2220,7 +2223,10 @@ __global__ __launch_bounds__(64, IMPLICIT ? 2 : 3) void gram_solve_kernel(
   for (int c = 0; c < CN; ++c) bt[c] = 0.f;
   int npos = 0;
   int chunk, light;
-  decode_task(blockIdx.x, n_chunks, n_light, chunk, light);
+  // rank 33-64 explicit: chunks and the longest light rows spread through the light
+  // list (task_order.h); the other instantiations were not measured with it
+  if constexpr (!IMPLICIT && CN == 4) decode_task_merged(blockIdx.x, n_chunks, n_light, chunk, light);
+  else decode_task(blockIdx.x, n_chunks, n_light, chunk, light);
   int64_t pb, pe;
   int row = -1;
   if (chunk >= 0) {
