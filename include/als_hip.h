@@ -519,6 +519,50 @@ int als_explain(const int64_t* row_ptr, const int32_t* col, const float* val, in
                 int32_t* n_used_out, int32_t* status_dev,
                 void* ws, size_t ws_bytes, void* stream);
 
+/* ---- K12: similar items / users (cosine nearest neighbours of a few query vectors among
+ *      the rows of one factor table; what Spark users do on the host over itemFactors, and
+ *      what other factorisation libraries offer as similar_items / similar_users) ---- */
+
+/* Added under ABI 9 without a version bump: three new symbols, nothing existing changes.
+ * als_similar: for each of the n_q query vectors Q [n_q, ldq] the `top` rows of the table
+ * T [n, ld] with the largest cosine, score = <q, t> / (|q| |t|) over columns [0, k) of the
+ * raw fp32 rows (columns [k, ld) and [k, ldq) are ignored, whatever they hold).  The grid
+ * runs over contiguous slices of T, one pass per 16 queries; |t|^2 comes from the registers
+ * that hold the row for the dot products: no normalised copy, no norm array and no pass
+ * over T before the sweep.  fp32 throughout except |q|, which is fp64; the dot errs by at
+ * most k 2^-24 |q||t|.  Order: score descending, ties by ascending row (the exact 64-bit
+ * key of als_topk), so the lists depend neither on `slices` nor on the order workgroups
+ * finish, and a (query, row) pair scores the same bits wherever it is computed.
+ * Never listed: row self_rows[q] (by index; -1 or a NULL self_rows: none — another row
+ * with the same factors is listed, at score 1); a row whose bit is clear in allow_bits
+ * (als_topk_filtered's mask; NULL: every row); a row whose fp32 |t|^2 is zero, NaN or Inf
+ * (an all-zero row, a row holding a NaN or an Inf; also one so small or so large that the
+ * fp32 sum of squares leaves the normal range).  A query with zero norm, a NaN or an Inf
+ * gets an empty list.  Empty and open slots: idx -1, score -inf.
+ * slices: 0 = 8 per compute unit, at most n / max(256, 2 top); otherwise the number of
+ * slices, 1 .. 4096.  Each slice writes `top` keys per query to the workspace with plain
+ * stores (no atomics); a second launch, one wavefront per query (two stages above 64
+ * slices), selects, ranks and unpacks them.
+ * 1 <= k <= 128 and 1 <= top <= 256 (ALS_EUNSUPPORTED outside); ld, ldq >= k and multiples
+ * of 4; T, Q and ws 16-byte aligned; n < 2^31 - 1.  Bad sizes, slices outside [0, 4096] and
+ * null pointers are ALS_EINVAL, a short workspace ALS_EWORKSPACE, all checked on the host
+ * before any launch; n_q == 0 is a no-op.  als_similar_workspace_bytes returns 0 for
+ * arguments als_similar rejects.
+ * als_similar_unit_rows: out [n, ld] = t / |t| per row (fp64 norm over columns [0, k),
+ * fp32 quotient, columns [k, ld) zero), for callers that hand a normalised table to
+ * als_topk_filtered.  A row that can be nobody's neighbour (zero norm, NaN, Inf) becomes
+ * zeros, has its bit cleared in allow_bits (nullable; ceil(n / 32) words, bits past n are
+ * cleared too) and 0 in valid_out (nullable, int32 [n], 1 otherwise).  One launch. */
+size_t als_similar_workspace_bytes(int64_t n, int32_t n_q, int32_t top, int32_t slices);
+int als_similar(const float* T, int64_t n, int32_t ld, int32_t k,
+                const float* Q, int64_t n_q, int32_t ldq,
+                const int32_t* self_rows, const uint32_t* allow_bits,
+                int32_t top, int32_t slices,
+                int32_t* idx_out, float* score_out,
+                void* ws, size_t ws_bytes, void* stream);
+int als_similar_unit_rows(const float* T, int64_t n, int32_t ld, int32_t k, float* out,
+                          uint32_t* allow_bits, int32_t* valid_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

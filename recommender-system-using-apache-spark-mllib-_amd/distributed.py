@@ -46,7 +46,7 @@ import torch.distributed as dist
 from .engine import id_offset
 from .filters import (reject_sharded_explain, reject_sharded_filters, reject_sharded_fold_in,
                       reject_sharded_full_rank, reject_sharded_objective,
-                      reject_sharded_regression)
+                      reject_sharded_regression, reject_sharded_similar)
 
 
 class HipKernels:
@@ -959,6 +959,14 @@ class ShardedALS:
                 user_side: bool = True, ratings=None):
         """ALSCore.explain is not offered on the sharded engine yet."""
         reject_sharded_explain()
+
+    def similar(self, ids, top: int, user_side: bool = False, *, candidates=None):
+        """ALSCore.similar is not offered on the sharded engine yet."""
+        reject_sharded_similar()
+
+    def similar_all(self, top: int, user_side: bool = False, *, candidates=None):
+        """ALSCore.similar_all is not offered on the sharded engine yet."""
+        reject_sharded_similar()
 
     def regression_metrics(self, users, items, ratings, through_origin: bool = False) -> dict:
         """ALSCore.regression_metrics is not offered on the sharded engine yet."""

@@ -616,6 +616,91 @@ def topk_rows_filtered(Q: torch.Tensor, n_q: int, V: torch.Tensor, n_v: int, ran
     return idx, sc
 
 
+SIMILAR_MAX_TOP = 256     # als_similar: neighbours per query
+SIMILAR_MAX_SLICES = 4096
+# Distinct query rows from which ALSCore.similar leaves the table sweep (K12, one pass over
+# the table per 16 queries) for the unit copy + K5 route (one set-up, then every query in
+# one sweep).  Set from the measured crossover: DESIGN.md section K12,
+# profiles/k12_similar_cost.json.
+SIMILAR_SWEEP_MIN_ROWS = 256
+
+
+def similar_rows(Q: torch.Tensor, n_q: int, T: torch.Tensor, n: int, rank: int, top: int,
+                 self_rows, allow_bits, slices: int = 0):
+    """K12 (als_similar): the `top` rows of the table T [n, ld] nearest in cosine to each of
+    the n_q query vectors Q [n_q, ldq], from the raw fp32 rows.  self_rows (int32 [n_q] or
+    None): the table row a query must never list, -1 for none; allow_bits: the
+    filters.pack_allow_bits mask or None; slices: 0 = auto (tests pin it).  Returns (idx
+    int32 [n_q, top], score f32 [n_q, top]), score descending, ties by ascending row;
+    empty slots idx -1, score -inf."""
+    n_q, n, rank, top, slices = int(n_q), int(n), int(rank), int(top), int(slices)
+    if not 1 <= top <= SIMILAR_MAX_TOP:
+        raise ValueError(f"top must be in [1, {SIMILAR_MAX_TOP}], got {top}")
+    if not 1 <= rank <= MAX_RANK:
+        raise ValueError(f"rank must be in [1, {MAX_RANK}], got {rank}")
+    if not 0 <= slices <= SIMILAR_MAX_SLICES:
+        raise ValueError(f"slices must be in [0, {SIMILAR_MAX_SLICES}] (0 = auto), got {slices}")
+    if n_q < 0 or n < 0:
+        raise ValueError("n_q and n must be >= 0")
+    L = _lib.lib()
+    dev = Q.device
+    idx = torch.empty((n_q, top), dtype=torch.int32, device=dev)
+    sc = torch.empty((n_q, top), dtype=torch.float32, device=dev)
+    w = torch.empty(max(int(L.als_similar_workspace_bytes(n, min(n_q, 16), top, slices)), 256),
+                    dtype=torch.uint8, device=dev)
+    check(L.als_similar(ptr(T), n, T.shape[1], rank, ptr(Q), n_q, Q.shape[1], ptr(self_rows),
+                        ptr(allow_bits), top, slices, ptr(idx), ptr(sc), ptr(w), w.numel(),
+                        stream_ptr(dev)), "als_similar")
+    return idx, sc
+
+
+def unit_rows(T: torch.Tensor, n: int, rank: int, allow_bits=None):
+    """als_similar_unit_rows: (unit-norm fp32 copy of T's first n rows, allow mask, valid
+    int32 [n]).  The mask is a copy of allow_bits (or all ones) with the bit of every row
+    that can be nobody's neighbour (zero norm, NaN, Inf) cleared, in the same launch; such
+    rows are zeros in the copy and 0 in valid."""
+    L = _lib.lib()
+    n = int(n)
+    dev = T.device
+    out = torch.empty((n, T.shape[1]), dtype=torch.float32, device=dev)
+    valid = torch.empty(n, dtype=torch.int32, device=dev)
+    if allow_bits is None:
+        bits = torch.full((max((n + 31) // 32, 1),), -1, dtype=torch.int32, device=dev)
+    else:
+        bits = allow_bits.clone()
+    check(L.als_similar_unit_rows(ptr(T), n, T.shape[1], int(rank), ptr(out), ptr(bits),
+                                  ptr(valid), stream_ptr(dev)), "als_similar_unit_rows")
+    return out, bits, valid
+
+
+def similar_rows_unit(rows: Optional[torch.Tensor], T: torch.Tensor, n: int, rank: int, top: int,
+                      allow_bits=None):
+    """The many-query route to similar_rows' contract, built from K5: a unit-norm copy of
+    the table (unit_rows) is both Q and V of topk_rows_filtered, each query excludes its own
+    row through the exclusion arrays (begin = r, end = r + 1 into col = arange(n)), and the
+    lists of query rows without a direction (zero norm, NaN, Inf) are blanked afterwards —
+    K5 would list the first rows by index at score 0.  rows: dense table rows (int64) that
+    are the queries, None = every row.  Scores agree with similar_rows within 1e-5; pairs
+    closer than that may be ordered differently by the two routes."""
+    if not 1 <= int(top) <= SIMILAR_MAX_TOP:
+        raise ValueError(f"top must be in [1, {SIMILAR_MAX_TOP}], got {top}")
+    n = int(n)
+    dev = T.device
+    Tn, bits, valid = unit_rows(T, n, rank, allow_bits)
+    col = torch.arange(max(n, 1), dtype=torch.int32, device=dev)
+    if rows is None:
+        Qn, beg, ok = Tn, torch.arange(n, dtype=torch.int64, device=dev), valid
+    else:
+        rows = rows.long()
+        Qn, beg, ok = Tn.index_select(0, rows).contiguous(), rows.contiguous(), valid[rows]
+    idx, sc = topk_rows_filtered(Qn, int(beg.numel()), Tn, n, rank, int(top), beg,
+                                 (beg + 1).contiguous(), col, bits)
+    dead = ok == 0
+    idx[dead] = -1
+    sc[dead] = float("-inf")
+    return idx, sc
+
+
 MAX_RANK_AT = 256  # als_rank_metrics: list positions scored per row
 
 
@@ -1148,6 +1233,63 @@ class ALSCore:
         Qs = Q.index_select(0, rows.long()).contiguous()
         idx, sc = self._topk(Qs, keys.numel(), user_side, top, exclude, candidates, rows.long())
         return keys, ids_of(oi.ids(), idx[:, :t]), sc[:, :t]
+
+    # ---- K12: which rows are like this one? ----
+    def _similar_args(self, top, user_side: bool, candidates):
+        """(index, table, t, kernel top, allow mask) of a neighbour search on one side."""
+        if self.U is None or self.V is None:
+            raise ValueError("similar needs factors: fit() the core or build it from_factors")
+        top = int(top)
+        if not 1 <= top <= SIMILAR_MAX_TOP:
+            raise ValueError(f"top must be in [1, {SIMILAR_MAX_TOP}], got {top}")
+        qi, T, _, _ = self._sides(user_side)
+        bits = None
+        if candidates is not None:
+            c = _to_device(candidates, torch.int32, self.device)
+            bits = _filters.pack_allow_bits(qi.rows_of(c), qi.n)
+        return qi, T, min(top, qi.n - 1), bits
+
+    def similar(self, ids, top: int, user_side: bool = False, *, candidates=None):
+        """Cosine nearest neighbours inside one side's factors: for the distinct known ids
+        of `ids` (ascending; unknown ids dropped, as recommend_subset drops them) the `top`
+        most similar OTHER rows of the same side — items by default, users with
+        user_side=True.  Returns (keys [m], ids [m, t], scores [m, t]) on the device,
+        t = min(top, n - 1), cosine descending, ties by ascending dense row.
+        candidates: ids of the same side the neighbours (not the queries) are restricted
+        to.  Never listed: the row itself (by index: a different row with the same factors
+        is, at similarity 1), and a row whose factors are all zero or hold a NaN / Inf;
+        such a row as a query gets an empty list.  Empty slots have score -inf.
+        Fewer than SIMILAR_SWEEP_MIN_ROWS queries sweep the raw table (K12, als_similar);
+        more take the unit copy + K5 route (similar_rows_unit).  Both keep this contract,
+        scores within 1e-5 of each other; neighbours closer than that may swap places."""
+        qi, T, t, bits = self._similar_args(top, user_side, candidates)
+        q = _to_device(ids, torch.int32, self.device)
+        keys = torch.unique(q)
+        rows = qi.rows_of(keys)
+        known = rows >= 0
+        keys, rows = keys[known], rows[known]
+        m = int(keys.numel())
+        if m == 0 or t == 0:
+            return keys, torch.empty((m, t), dtype=torch.int32, device=self.device), \
+                torch.empty((m, t), dtype=torch.float32, device=self.device)
+        if m >= SIMILAR_SWEEP_MIN_ROWS:
+            idx, sc = similar_rows_unit(rows, T, qi.n, self.rank, t, bits)
+        else:
+            Q = T.index_select(0, rows).contiguous()
+            idx, sc = similar_rows(Q, m, T, qi.n, self.rank, t, rows.to(torch.int32).contiguous(),
+                                   bits)
+        return keys, ids_of(qi.ids(), idx), sc
+
+    def similar_all(self, top: int, user_side: bool = False, *, candidates=None):
+        """similar for every row of the side, in dense order: (keys [n], ids [n, t], scores
+        [n, t]).  One unit-norm copy of the table, then one K5 sweep with the copy on both
+        sides (never n / 16 passes of K12)."""
+        qi, T, t, bits = self._similar_args(top, user_side, candidates)
+        if t == 0:
+            return qi.ids(), torch.empty((qi.n, 0), dtype=torch.int32, device=self.device), \
+                torch.empty((qi.n, 0), dtype=torch.float32, device=self.device)
+        idx, sc = similar_rows_unit(None, T, qi.n, self.rank, t, bits)
+        return qi.ids(), ids_of(qi.ids(), idx), sc
 
     # ---- K7: rows the model has never seen ----
     def _fold_in(self, ids, other_ids, ratings, reg, implicit, alpha, user_side):

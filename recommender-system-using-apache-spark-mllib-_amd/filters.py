@@ -19,7 +19,8 @@ import torch
 
 __all__ = ["pack_allow_bits", "exclusion_lists", "relevance_lists", "ragged_rows",
            "relevance_lists_weighted", "reject_sharded_filters", "reject_sharded_fold_in",
-           "reject_sharded_regression", "reject_sharded_full_rank", "reject_sharded_explain"]
+           "reject_sharded_regression", "reject_sharded_full_rank", "reject_sharded_explain",
+           "reject_sharded_similar"]
 
 
 def pack_allow_bits(rows: torch.Tensor, n_v: int) -> torch.Tensor:
@@ -133,6 +134,15 @@ def reject_sharded_explain() -> None:
         "explain is not supported by the sharded engine (ShardedALS) yet: explain scores on "
         "a single-GPU ALSCore (e.g. ALSCore.from_factors over the gathered factors, with "
         "ratings=)")
+
+
+def reject_sharded_similar() -> None:
+    """The sharded engine carries similar / similar_all with the single-GPU signature and
+    refuses them, as it refuses explain."""
+    raise NotImplementedError(
+        "similar / similar_all are not supported by the sharded engine (ShardedALS) yet: "
+        "search neighbours on a single-GPU ALSCore (e.g. ALSCore.from_factors over the "
+        "gathered factors)")
 
 
 def reject_sharded_regression() -> None:

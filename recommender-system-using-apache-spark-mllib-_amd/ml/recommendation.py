@@ -513,6 +513,51 @@ class ALSModel:
         return pd.DataFrame({p["userCol"]: uu, p["itemCol"]: ii, p["predictionCol"]: sc,
                              "contributions": lists})
 
+    # -- similar items / users (K12): cosine nearest neighbours inside one side's factors --
+    def _similar_ids(self, dataset_or_ids, col: str):
+        """A dataset holding `col` (read with columns_of, as recommendForItemSubset reads
+        it), or plain ids: a scalar or a one-dimensional sequence / array / tensor."""
+        x = dataset_or_ids
+        if isinstance(x, torch.Tensor) and x.dim() <= 1:
+            x = x.detach().cpu().numpy()
+        if np.isscalar(x) or (isinstance(x, np.ndarray) and x.ndim <= 1 and not x.dtype.names) \
+                or (isinstance(x, (list, tuple)) and all(np.isscalar(v) for v in x)):
+            return check_integers(np.asarray(x).reshape(-1), col)
+        return check_integers(columns_of(x, (col,))[0], col)
+
+    def _similar_df(self, key_col, keys, ids, sc):
+        df = self._recs_df(key_col, keys, ids, sc)
+        return df.rename(columns={"recommendations": "similar"})
+
+    def _similar(self, dataset_or_ids, num, user_side: bool, candidates):
+        col = self._p["userCol" if user_side else "itemCol"]
+        if candidates is not None:
+            candidates = check_integers(np.asarray(candidates).reshape(-1), col)
+        return self._similar_df(col, *self._core.similar(
+            self._similar_ids(dataset_or_ids, col), int(num), user_side, candidates=candidates))
+
+    def similarItems(self, dataset_or_ids, numItems: int, *, candidates=None):
+        """Which items are like these?  DataFrame[itemCol, similar: list of (item,
+        similarity)] for the distinct known items of `dataset_or_ids` (a dataset with the
+        item column, or item ids): the numItems nearest other items by the cosine of their
+        factors, most similar first (ties: lower dense row first).  candidates= restricts
+        the neighbours (not the queries) to those item ids.  An item is never its own
+        neighbour; items whose factors are all zero or not finite are nobody's, and get an
+        empty list.  Works on a loaded model: the factors alone suffice."""
+        return self._similar(dataset_or_ids, numItems, False, candidates)
+
+    def similarUsers(self, dataset_or_ids, numUsers: int, *, candidates=None):
+        """similarItems among the user factors: DataFrame[userCol, similar]."""
+        return self._similar(dataset_or_ids, numUsers, True, candidates)
+
+    def similarItemsForAllItems(self, numItems: int, *, candidates=None):
+        """similarItems for every item of the model, one device sweep for all of them."""
+        col = self._p["itemCol"]
+        if candidates is not None:
+            candidates = check_integers(np.asarray(candidates).reshape(-1), col)
+        return self._similar_df(col, *self._core.similar_all(int(numItems), False,
+                                                             candidates=candidates))
+
     def recommendForItemSubset(self, dataset, numUsers: int, *, exclude=None, candidates=None):
         col = self._p["itemCol"]
         ids = check_integers(columns_of(dataset, (col,))[0], col)

@@ -187,6 +187,28 @@ class MatrixFactorizationModel:
                        candidates=None) -> List[Rating]:
         return self._one(int(product), num, False, exclude, candidates)
 
+    def _similar_one(self, key, num, user_side, candidates):
+        if candidates is not None:
+            candidates = check_integers(np.asarray(candidates).reshape(-1),
+                                        "user" if user_side else "product")
+        keys, ids, sc = self._core.similar([int(key)], int(num), user_side,
+                                           candidates=candidates)
+        if keys.numel() == 0:
+            raise KeyError(f"unknown id {key}")
+        ids, sc = ids.cpu().numpy()[0], sc.cpu().numpy()[0]
+        return [(int(a), float(s)) for a, s in zip(ids, sc) if np.isfinite(s)]
+
+    def similarProducts(self, product: int, num: int, *, candidates=None):
+        """The `num` products most like `product`: [(product, similarity)], the cosine of the
+        product factors, most similar first (K12).  candidates= restricts the neighbours to
+        those product ids.  The product itself is never listed; products whose factors are
+        all zero or not finite are nobody's neighbour.  KeyError for an unknown product."""
+        return self._similar_one(int(product), num, False, candidates)
+
+    def similarUsers(self, user: int, num: int, *, candidates=None):
+        """similarProducts among the user factors: [(user, similarity)]."""
+        return self._similar_one(int(user), num, True, candidates)
+
     def recommendProductsForUsers(self, num: int, *, exclude=None, candidates=None):
         keys, ids, sc = self._core.recommend_all(int(num), True,
                                                  **self._filters(exclude, candidates, True))

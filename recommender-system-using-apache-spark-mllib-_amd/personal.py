@@ -20,7 +20,7 @@ from typing import Dict, Iterable, List, Sequence, Tuple
 import numpy as np
 
 __all__ = ["movie_counts_and_averages", "personal_recommendations",
-           "personal_recommendations_fold_in", "personal_explanations"]
+           "personal_recommendations_fold_in", "personal_explanations", "similar_movies"]
 
 
 def movie_counts_and_averages(ratings) -> Dict[int, Tuple[int, float]]:
@@ -112,6 +112,38 @@ def personal_explanations(model, rated: Iterable[Sequence], movies: Iterable[Seq
              [(name(a), float(b), float(c))
               for a, b, c in zip(ids[p, :n[p]], rat[p, :n[p]], con[p, :n[p]])])
             for p in range(len(ii)) if not np.isnan(sc[p])]
+
+
+def similar_movies(model, movie_ids: Iterable[int], movies: Iterable[Sequence], num: int = 10,
+                   min_ratings=None, ratings=None
+                   ) -> List[Tuple[str, List[Tuple[str, float]]]]:
+    """"Which movies are like this one?": for each movie of `movie_ids` the model knows
+    (ascending id), (movie name, [(neighbour's name, similarity), ...]) — the `num` movies
+    whose factors have the largest cosine with its own, most similar first (K12).
+
+    movies: (MovieID, title) pairs; a movie without a title is named by its id
+    min_ratings with ratings: neighbours are restricted to the movies with MORE than
+        min_ratings ratings in `ratings` ((user, movie, rating) triples, counted by
+        movie_counts_and_averages): the reference's R:245 "more than 75 ratings" filter
+        applied to neighbours.  The queried movies themselves need not pass it."""
+    titles = {}
+    for m, t in movies:
+        titles.setdefault(int(m), str(t))
+    want = [int(m) for m in movie_ids if -(2 ** 31) <= int(m) < 2 ** 31]
+    if not want:
+        return []
+    cand = None
+    if min_ratings is not None:
+        if ratings is None:
+            raise ValueError("min_ratings needs ratings= to count from")
+        counts = movie_counts_and_averages(ratings)
+        cand = np.asarray([m for m, (c, _) in counts.items()
+                           if c > min_ratings and -(2 ** 31) <= m < 2 ** 31], np.int32)
+    keys, ids, sc = (x.cpu().numpy() for x in _engine_of(model).similar(
+        np.asarray(want, np.int32), int(num), False, candidates=cand))
+    name = lambda a: titles.get(int(a), str(int(a)))
+    return [(name(k), [(name(a), float(s)) for a, s in zip(ri, rs) if np.isfinite(s)])
+            for k, ri, rs in zip(keys, ids, sc)]
 
 
 def personal_recommendations(model, user_id: int, rated: Iterable[Sequence],
