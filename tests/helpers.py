@@ -30,6 +30,175 @@ def planted(n_users, n_items, density=0.05, k_true=8, seed=0, heavy_items=(), he
     return (u * id_gap).astype(np.int32), (i * id_gap).astype(np.int32), r.astype(np.float32)
 
 
+def degree_rows(degrees, n_src, seed, ratings="stars"):
+    """Destination rows with exactly the given degrees (>= 1; distinct source ids each,
+    `rng.choice`) plus one row rating every source id, so both id maps are dense and
+    destination row t has degrees[t] ratings in the order returned here (the CSR build is
+    a stable sort).  "stars": planted half-star ratings in [0.5, 5]; "signed": the same
+    minus 2.5 (implicit preferences: positive, negative and exactly zero all occur).
+    Returns (dst, src, r) int32 / int32 / float32."""
+    if ratings not in ("stars", "signed"):
+        raise ValueError(f"ratings must be 'stars' or 'signed', got {ratings!r}")
+    degrees = [int(d) for d in degrees]
+    if min(degrees) < 1 or max(degrees) > n_src:
+        raise ValueError("degrees must lie in [1, n_src]")
+    rng = np.random.default_rng(seed)
+    dst = [np.full(d, t) for t, d in enumerate(degrees)]
+    src = [rng.choice(n_src, d, replace=False) for d in degrees]
+    dst.append(np.full(n_src, len(degrees)))
+    src.append(np.arange(n_src))
+    dst = np.concatenate(dst).astype(np.int32)
+    src = np.concatenate(src).astype(np.int32)
+    df = rng.normal(0, 0.35, (len(degrees) + 1, 8))
+    sf = rng.normal(0, 0.35, (n_src, 8))
+    r = np.clip(np.round((3.6 + (df[dst] * sf[src]).sum(1) + rng.normal(0, 0.8, len(dst))) * 2) / 2,
+                0.5, 5)
+    if ratings == "signed":
+        r = r - 2.5
+    return dst, src, r.astype(np.float32)
+
+
+def fp32_textbook_half_sweep(indptr, indices, vals, Y, reg, implicit=False, alpha=1.0, yty=None):
+    """computeFactors in textbook fp32 (the yardstick of DESIGN §2): per destination row
+    the normal equations accumulated one rating at a time with every product and sum in
+    np.float32 (NormalEquation.add: explicit ata += y y^T, atb += r y; implicit
+    c1 = alpha |r|, ata += c1 y y^T, atb += (1 + c1) y if r > 0, numExplicits = ratings
+    > 0, ata starting from YtY), ata_ii += regParam * numExplicits, LAPACK spotrf
+    (np.linalg.cholesky of a float32 matrix) and two fp32 triangular solves.
+    yty: [k, k] (implicit; rounded to fp32).  Returns X [n, k] float32."""
+    f32 = np.float32
+    Y = np.asarray(Y, f32)
+    vals = np.asarray(vals, f32)
+    n, k = len(indptr) - 1, Y.shape[1]
+    X = np.zeros((n, k), f32)
+    G0 = np.asarray(yty, np.float64).astype(f32) if implicit else np.zeros((k, k), f32)
+    tmp = np.empty((k, k), f32)
+    dg = np.arange(k)
+    for row in range(n):
+        A = G0.copy()
+        b = np.zeros(k, f32)
+        n_exp = 0
+        for p in range(int(indptr[row]), int(indptr[row + 1])):
+            y = Y[indices[p]]
+            r = vals[p]
+            if implicit:
+                c1 = f32(alpha) * np.abs(r)
+                np.multiply((c1 * y)[:, None], y[None, :], out=tmp)
+                if r > 0:
+                    b += (f32(1) + c1) * y
+                    n_exp += 1
+            else:
+                np.multiply(y[:, None], y[None, :], out=tmp)
+                b += r * y
+                n_exp += 1
+            A += tmp
+        A[dg, dg] += f32(reg) * f32(n_exp)
+        L = np.linalg.cholesky(A)
+        assert L.dtype == f32
+        z = np.zeros(k, f32)
+        for i in range(k):  # L z = b
+            z[i] = (b[i] - np.dot(L[i, :i], z[:i])) / L[i, i]
+        x = np.zeros(k, f32)
+        for i in range(k - 1, -1, -1):  # L^T x = z
+            x[i] = (z[i] - np.dot(L[i + 1:, i], x[i + 1:])) / L[i, i]
+        X[row] = x
+    return X
+
+
+# The K2/K3 edge grid (test_gpu_edges_k2_k3.py, test_k2k3_edges_cpu.py): task lengths around
+# every 32-rating MFMA step, 64-rating staging block and 128 / 512-rating task boundary.
+K2K3_DEGREES = (1, 2, 3, 7, 8, 9, 15, 16, 17, 31, 32, 33, 47, 63, 64, 65, 95, 96, 97, 127, 128,
+                129, 159, 160, 161, 191, 192, 193, 255, 256, 257, 287, 288, 289, 383, 384, 385,
+                511, 512, 513, 769, 1024)
+K2K3_RANKS = (1, 3, 15, 16, 17, 31, 32, 33, 47, 63, 64, 65, 97, 127, 128)
+K2K3_N_SRC = 1024
+K2K3_REG = 0.1
+K2K3_REPEATS = 3
+
+
+def k2k3_grid_degrees(rank):
+    """Every grid degree K2K3_REPEATS times (different source ids), with rank - 1, rank,
+    rank + 1 (a row has at least one rating)."""
+    return [d for d in K2K3_DEGREES + (rank - 1, rank, rank + 1) if d >= 1] * K2K3_REPEATS
+
+
+def unit_source_factors(n, k, seed):
+    """Seeded unit-norm Gaussian rows, fp32 (Spark's ALS.initialize shape)."""
+    x = np.random.default_rng(seed).standard_normal((n, k)).astype(np.float32)
+    return (x / np.linalg.norm(x.astype(np.float64), axis=1, keepdims=True)).astype(np.float32)
+
+
+_K2K3_CASES = {}
+
+
+def k2k3_grid_case(rank, implicit):
+    """The §1 inputs of one rank, shared (and left unchanged) by every test that needs
+    them: (dst, src, r) of degree_rows, the destination side's CSR, unit-norm source
+    factors Y.  The chunk, the dual switch and alpha do not change them."""
+    key = (rank, bool(implicit))
+    if key not in _K2K3_CASES:
+        from oracle import als_oracle as O
+        degrees = k2k3_grid_degrees(rank)
+        dst, src, r = degree_rows(degrees, K2K3_N_SRC, seed=rank,
+                                  ratings="signed" if implicit else "stars")
+        indptr, indices, vals = O.csr_build(dst, src, r, len(degrees) + 1)
+        Y = unit_source_factors(K2K3_N_SRC, rank, seed=1000 + rank)
+        _K2K3_CASES[key] = dict(degrees=degrees, dst=dst, src=src, r=r, indptr=indptr,
+                                indices=indices, vals=vals, Y=Y)
+    return _K2K3_CASES[key]
+
+
+_K2K3_REFS = {}
+
+
+def k2k3_grid_refs(rank, implicit, alpha=1.0):
+    """(fp64 oracle X, per-row relative errors of the fp32 textbook solve against it) on
+    the §1 inputs, computed once per (rank, mode)."""
+    key = (rank, bool(implicit), float(alpha) if implicit else 1.0)
+    if key not in _K2K3_REFS:
+        from oracle import als_oracle as O
+        c = k2k3_grid_case(rank, implicit)
+        a = (c["indptr"], c["indices"], c["vals"], c["Y"], K2K3_REG, implicit, alpha)
+        X = O.half_sweep(*a)
+        Xt = fp32_textbook_half_sweep(*a, yty=O.yty(c["Y"]) if implicit else None)
+        _K2K3_REFS[key] = (X, rel_row_errs(Xt, X))
+    return _K2K3_REFS[key]
+
+
+K2K3_SPECIAL_DEGREES = (1, 32, 33, 64, 65, 129)
+_K2K3_SPECIAL = {}
+
+
+def k2k3_special_rows(rank):
+    """Implicit rows that random data meets only by chance, one per degree of
+    K2K3_SPECIAL_DEGREES and kind: "nonpositive" (every rating <= 0: numExplicits = 0, a
+    zero right-hand side), "zero" (every rating exactly 0: confidence 0 as well) and
+    "last_positive" (one rating > 0, in the row's last position — alone in its staging
+    block at 65 and 129 ratings), among ordinary signed rows.  rows[kind][j] is the row of
+    degree K2K3_SPECIAL_DEGREES[j]."""
+    if rank not in _K2K3_SPECIAL:
+        from oracle import als_oracle as O
+        kinds = ("nonpositive", "zero", "last_positive", "ordinary")
+        degrees = list(K2K3_SPECIAL_DEGREES) * len(kinds)
+        dst, src, r = degree_rows(degrees, K2K3_N_SRC, seed=2000 + rank, ratings="signed")
+        nd = len(K2K3_SPECIAL_DEGREES)
+        rows = {kind: list(range(j * nd, (j + 1) * nd)) for j, kind in enumerate(kinds)}
+        for row in rows["nonpositive"] + rows["last_positive"]:
+            sel = np.nonzero(dst == row)[0]
+            r[sel] = -np.abs(r[sel])
+            r[sel[0]] = -1.5
+        for row in rows["zero"]:
+            r[dst == row] = 0.0
+        for row in rows["last_positive"]:
+            r[np.nonzero(dst == row)[0][-1]] = 2.0
+        del rows["ordinary"]
+        indptr, indices, vals = O.csr_build(dst, src, r, len(degrees) + 1)
+        Y = unit_source_factors(K2K3_N_SRC, rank, seed=3000 + rank)
+        _K2K3_SPECIAL[rank] = dict(degrees=K2K3_SPECIAL_DEGREES, rows=rows, dst=dst, src=src, r=r,
+                                   indptr=indptr, indices=indices, vals=vals, Y=Y)
+    return _K2K3_SPECIAL[rank]
+
+
 def rel_row_err(x, ref):
     x = np.asarray(x, np.float64)
     ref = np.asarray(ref, np.float64)
