@@ -563,6 +563,50 @@ int als_similar(const float* T, int64_t n, int32_t ld, int32_t k,
 int als_similar_unit_rows(const float* T, int64_t n, int32_t ld, int32_t k, float* out,
                           uint32_t* allow_bits, int32_t* valid_out, void* stream);
 
+/* ---- K13: nonnegative rows (Spark's `nonnegative=true`: computeFactors with NNLSSolver
+ *      in place of CholeskySolver, mllib/optimization/NNLS.scala) -------------------- */
+
+/* Added under ABI 9 without a version bump: two new symbols, nothing existing changes.
+ * als_nnls_rows: the factor row x >= 0 that minimises x^T A x / 2 - b^T x for each of the
+ * n_rows ragged rows, with A and b EXACTLY als_fold_in's (above): the same input layout
+ * (row_ptr int64, col int32 dense rows of Y_src, val fp32; a RatingBlock's CSR has this
+ * shape, so the call serves a training half-sweep and a fold-in alike), the same skipping of
+ * unknown columns (col < 0 or >= n_src: not counted), the same sums in fp64 over the fp32
+ * factors in rating order, the same reg * n (explicit) / reg * n+ (implicit) diagonal and
+ * the same yty_packed (required iff implicit).  Columns [k, ld) of Y_src are ignored
+ * whatever they hold.
+ * The solver is Spark's NNLS.solve in fp64: from x = 0, projected-gradient steps with
+ * conjugate-gradient directions (dropped for one iteration after a coordinate hits the
+ * wall), the exact line minimum clamped so that no coordinate goes negative, at most
+ * max(400, 20 k) iterations, stopped when the step is NaN, below 1e-7 or above 1e40, or the
+ * squared direction is below 1e-12 |x|^2 or 1e-32.  The step test also stops a row at x = 0
+ * whose A has eigenvalues above ~1e7 (tens of millions of ratings, or factors of norm 1e4):
+ * that is Spark's behaviour and is reproduced, not repaired.  No row fails: a row with
+ * b = 0 (no used entry; implicit without a positive rating) is all zeros at the first test.
+ * X_out[r*ld_out ..] gets the fp32 solution in columns [0, k), every value >= 0, and zeros
+ * in [k, ld_out).  n_used_out (nullable): the used entries of row r.  iters_out (nullable,
+ * int32 [n_rows]): the iteration count at return.  Two calls give bit-identical output.
+ * A row with more than `chunk` ratings is cut into chunk-rating tasks, one workgroup each,
+ * whose fp64 partial (A, b, n, n+) go to workspace slots and are summed in slot order before
+ * the solve, so a long row never runs serially; rows are solved longest first (sorted by
+ * degree on the device).  als_nnls_workspace_bytes(n_rows, nnz, k, chunk) sizes the
+ * workspace for any rows with nnz entries in all (0 for arguments als_nnls_rows rejects);
+ * with a smaller workspace that still holds the per-row arrays, the long rows its slots
+ * cannot take are summed serially (same result up to the order of the fp64 sums).
+ * 1 <= k <= 128 (ALS_EUNSUPPORTED outside); ld, ld_out >= k and multiples of 4; Y_src, X_out
+ * and ws 16-byte aligned; n_rows < 2^31 - 1, n_src < 2^31, chunk >= 1.  Null pointers,
+ * reg < 0, alpha < 0, implicit without yty_packed and n_rows < 0 are ALS_EINVAL, a workspace
+ * too small for the per-row arrays ALS_EWORKSPACE, all checked on the host before any device
+ * call; n_rows == 0 is a no-op returning 0.
+ * Parity bar: 1e-4 relative per row against the fp64 restatement tests/nnls_ref.py; measured
+ * maxima and the KKT residuals are in DESIGN.md section K13 and tests/test_gpu_nnls.py. */
+size_t als_nnls_workspace_bytes(int64_t n_rows, int64_t nnz, int32_t k, int32_t chunk);
+int als_nnls_rows(const int64_t* row_ptr, const int32_t* col, const float* val, int64_t n_rows,
+                  const float* Y_src, int64_t n_src, int32_t ld, int32_t k,
+                  float reg, int implicit, float alpha, const double* yty_packed,
+                  int32_t chunk, float* X_out, int32_t ld_out, int32_t* n_used_out,
+                  int32_t* iters_out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,9 @@ SIGNATURES = {
     "als_similar_workspace_bytes": (SZ, [I64, I32, I32, I32]),
     "als_similar": (ctypes.c_int, [P, I64, I32, I32, P, I64, I32, P, P, I32, I32, P, P, P, SZ, P]),
     "als_similar_unit_rows": (ctypes.c_int, [P, I64, I32, I32, P, P, P, P]),
+    "als_nnls_workspace_bytes": (SZ, [I64, I64, I32, I32]),
+    "als_nnls_rows": (ctypes.c_int, [P, P, P, I64, P, I64, I32, I32, F32, ctypes.c_int, F32, P,
+                                     I32, P, I32, P, P, P, SZ, P]),
 }
 
 ABI_VERSION = 9

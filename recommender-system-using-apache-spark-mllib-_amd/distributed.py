@@ -45,8 +45,9 @@ import torch.distributed as dist
 
 from .engine import id_offset
 from .filters import (reject_sharded_explain, reject_sharded_filters, reject_sharded_fold_in,
-                      reject_sharded_full_rank, reject_sharded_objective,
-                      reject_sharded_regression, reject_sharded_similar)
+                      reject_sharded_full_rank, reject_sharded_nonnegative,
+                      reject_sharded_objective, reject_sharded_regression,
+                      reject_sharded_similar)
 
 
 class HipKernels:
@@ -787,11 +788,14 @@ class ShardedALS:
 
     def fit(self, rank, max_iter, reg, implicit=False, alpha=1.0, seed=0, U0=None,
             U0_global=None, checkpoint_dir=None, checkpoint_interval=10, resume=False,
-            objective_every=0, tol=None):
+            objective_every=0, tol=None, nonnegative=False):
         """ALSCore.fit's contract.  Checkpoints hold the dense global factors (written
         by process 0, read by every rank), so a job may resume on another world size.
-        objective_every / tol (K10) are carried with the single-GPU signature and refused."""
+        objective_every / tol (K10) and nonnegative (K13) are carried with the single-GPU
+        signature and refused."""
         from . import checkpoint as C
+        if nonnegative:
+            reject_sharded_nonnegative()
         if objective_every or tol is not None:
             reject_sharded_objective()
         init = C.init_key(seed, U0 if U0 is not None else U0_global) if checkpoint_dir else None
@@ -946,12 +950,13 @@ class ShardedALS:
             "factors)")
 
     def fold_in(self, ids, other_ids, ratings, *, reg, implicit=False, alpha=1.0,
-                user_side: bool = True):
+                user_side: bool = True, nonnegative: bool = False):
         """ALSCore.fold_in is not offered on the sharded engine yet."""
         reject_sharded_fold_in()
 
     def recommend_new(self, ids, other_ids, ratings, top: int, *, reg, implicit=False, alpha=1.0,
-                      user_side: bool = True, exclude_rated: bool = True, candidates=None):
+                      user_side: bool = True, exclude_rated: bool = True, candidates=None,
+                      nonnegative: bool = False):
         """ALSCore.recommend_new is not offered on the sharded engine yet."""
         reject_sharded_fold_in()
 

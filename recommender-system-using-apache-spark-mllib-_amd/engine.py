@@ -426,6 +426,40 @@ def fold_in_rows(row_ptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, Y:
     return X, n_used
 
 
+def nnls_rows(row_ptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, Y: torch.Tensor,
+              n_src: int, rank: int, reg: float, implicit: bool, alpha: float,
+              yty: Optional[torch.Tensor], ws: Workspace, chunk: int = DEFAULT_CHUNK,
+              X: Optional[torch.Tensor] = None, iters: bool = False):
+    """K13 (als_nnls_rows): fold_in_rows' rows solved under x >= 0 by Spark's NNLS solver —
+    the same ragged input (a RatingBlock's row_ptr / col / val included) and the same
+    normal equations, in three launches plus a device sort of the rows by degree.  chunk:
+    ratings per task of a longer row.  X: the f32 [n, ld] table to write (a half-sweep's
+    destination factors); None allocates [n, ld_for(rank)].  Returns (X, n_used int32 [n],
+    iterations int32 [n] or None).  No row fails and there is no status word."""
+    L = _lib.lib()
+    n = int(row_ptr.numel()) - 1
+    dev = Y.device
+    if X is None:
+        X = torch.empty((n, ld_for(rank)), dtype=torch.float32, device=dev)
+    n_used = torch.empty(n, dtype=torch.int32, device=dev)
+    it = torch.empty(n, dtype=torch.int32, device=dev) if iters else None
+    if n == 0:
+        return X, n_used, it
+    if col.numel() == 0:  # rows without a single entry: never read, but not null
+        col = torch.zeros(1, dtype=torch.int32, device=dev)
+        val = torch.zeros(1, dtype=torch.float32, device=dev)
+        nnz = 0
+    else:
+        nnz = int(col.numel())
+    need = int(L.als_nnls_workspace_bytes(n, nnz, rank, int(chunk)))
+    w = ws.get(need)
+    check(L.als_nnls_rows(ptr(row_ptr), ptr(col), ptr(val), n, ptr(Y), int(n_src), Y.shape[1],
+                          rank, float(reg), int(bool(implicit)), float(alpha), ptr(yty),
+                          int(chunk), ptr(X), X.shape[1], ptr(n_used), ptr(it), ptr(w),
+                          max(need, 256), stream_ptr(dev)), "als_nnls_rows")
+    return X, n_used, it
+
+
 EXPLAIN_MAX_TOP = 32
 
 
@@ -991,20 +1025,40 @@ class ALSCore:
                 setattr(self, name, schedule_block(b.n_rows, b.nnz, b.row_ptr, b.col, b.val,
                                                    self.ws, chunk))
 
-    def half_sweep_items(self, reg, implicit=False, alpha=1.0):
+    def _half_sweep_nnls(self, block, Y, n_src, X, reg, implicit, alpha):
+        """One computeFactors pass with Spark's NNLSSolver (K13); a buffer of its own, so the
+        solve workspace keeps its rating scale."""
+        if getattr(self, "ws_nnls", None) is None:
+            self.ws_nnls = Workspace(self.device)
+        yty = compute_yty(Y, n_src, self.rank, self.ws_yty) if implicit else None
+        nnls_rows(block.row_ptr, block.col, block.val, Y, n_src, self.rank, reg, implicit, alpha,
+                  yty, self.ws_nnls, DEFAULT_CHUNK, X=X)
+
+    def half_sweep_items(self, reg, implicit=False, alpha=1.0, nonnegative=False):
+        if nonnegative:
+            return self._half_sweep_nnls(self.item_block, self.U, self.n_users, self.V, reg,
+                                         implicit, alpha)
         self.schedule_for(implicit)
         yty = compute_yty(self.U, self.n_users, self.rank, self.ws_yty) if implicit else None
         solve_half(self.item_block, self.U, self.V, self.rank, reg, implicit, alpha, yty,
                    self.status, self.ws)
 
-    def half_sweep_users(self, reg, implicit=False, alpha=1.0):
+    def half_sweep_users(self, reg, implicit=False, alpha=1.0, nonnegative=False):
+        if nonnegative:
+            return self._half_sweep_nnls(self.user_block, self.V, self.n_items, self.U, reg,
+                                         implicit, alpha)
         self.schedule_for(implicit)
         yty = compute_yty(self.V, self.n_items, self.rank, self.ws_yty) if implicit else None
         solve_half(self.user_block, self.V, self.U, self.rank, reg, implicit, alpha, yty,
                    self.status, self.ws)
 
-    def iterate(self, reg, implicit=False, alpha=1.0):
-        """One ALS iteration in Spark's order: items from users, then users from items."""
+    def iterate(self, reg, implicit=False, alpha=1.0, nonnegative=False):
+        """One ALS iteration in Spark's order: items from users, then users from items.
+        nonnegative: every row is solved under x >= 0 (K13, Spark's NNLSSolver)."""
+        if nonnegative:
+            self.half_sweep_items(reg, implicit, alpha, nonnegative=True)
+            self.half_sweep_users(reg, implicit, alpha, nonnegative=True)
+            return
         self.half_sweep_items(reg, implicit, alpha)
         self.half_sweep_users(reg, implicit, alpha)
 
@@ -1051,7 +1105,7 @@ class ALSCore:
 
     def fit(self, rank, max_iter, reg, implicit=False, alpha=1.0, seed=0, U0=None,
             checkpoint_dir=None, checkpoint_interval=10, resume=False, objective_every=0,
-            tol=None):
+            tol=None, nonnegative=False):
         """max_iter ALS iterations from the seeded (or given U0) start.  checkpoint_dir:
         write U, V every checkpoint_interval iterations (checkpoint.py); resume
         (True / "auto"): continue from the checkpoint there at its iteration.
@@ -1061,8 +1115,17 @@ class ALSCore:
         after an evaluated iteration whose decrease L_prev - L_cur <= tol * L_prev (tol
         alone evaluates every iteration); a checkpoint due at that iteration is still
         written.  self.iterations_run is where the fit stopped.  With both off (the default)
-        nothing is evaluated and no host sync is added."""
+        nothing is evaluated and no host sync is added.
+        nonnegative: Spark's `nonnegative=true` — the same seeded signed start, then every
+        half-sweep solves its rows under x >= 0 (K13), so all factors are >= 0 from the first
+        one on; objective_every / tol evaluate the same objective.  Not with checkpoint_dir:
+        a checkpoint does not record the solver, and resuming a Cholesky fit as NNLS (or
+        the reverse) must not happen silently."""
         from . import checkpoint as C
+        nonnegative = bool(nonnegative)
+        if nonnegative and checkpoint_dir:
+            raise ValueError("nonnegative=True cannot be combined with checkpoint_dir: a "
+                             "checkpoint does not record the solver")
         every = int(objective_every)
         if every < 0:
             raise ValueError(f"objective_every must be >= 0, got {objective_every}")
@@ -1082,7 +1145,10 @@ class ALSCore:
         self.iterations_run = start
         prev = None
         for it in range(start, max_iter):
-            self.iterate(reg, implicit, alpha)
+            if nonnegative:
+                self.iterate(reg, implicit, alpha, nonnegative=True)
+            else:
+                self.iterate(reg, implicit, alpha)
             stop = False
             if every and ((it + 1) % every == 0 or it + 1 == max_iter):
                 cur = self.objective(reg, implicit, alpha)["objective"]
@@ -1292,7 +1358,8 @@ class ALSCore:
         return qi.ids(), ids_of(qi.ids(), idx), sc
 
     # ---- K7: rows the model has never seen ----
-    def _fold_in(self, ids, other_ids, ratings, reg, implicit, alpha, user_side):
+    def _fold_in(self, ids, other_ids, ratings, reg, implicit, alpha, user_side,
+                 nonnegative=False):
         """(keys, X [m, ld], n_used, row_ptr, col) of fold_in, X with its padding columns."""
         if self.U is None or self.V is None:
             raise ValueError("fold_in needs factors: fit() the core or build it from_factors")
@@ -1308,6 +1375,10 @@ class ALSCore:
                                       device=self.device),
                     torch.empty(0, dtype=torch.int32, device=self.device), row_ptr, col)
         yty = compute_yty(Y, oi.n, self.rank, self.ws_yty) if implicit else None
+        if nonnegative:
+            X, n_used, _ = nnls_rows(row_ptr, col, val, Y, oi.n, self.rank, reg, implicit, alpha,
+                                     yty, self.ws)
+            return keys, X, n_used, row_ptr, col
         status = torch.zeros(1, dtype=torch.int32, device=self.device)
         X, n_used = fold_in_rows(row_ptr, col, val, Y, oi.n, self.rank, reg, implicit, alpha, yty,
                                  status, self.ws)
@@ -1315,7 +1386,7 @@ class ALSCore:
         return keys, X, n_used, row_ptr, col
 
     def fold_in(self, ids, other_ids, ratings, *, reg, implicit=False, alpha=1.0,
-                user_side: bool = True):
+                user_side: bool = True, nonnegative: bool = False):
         """Factor rows for rows the model was not fitted on, without a refit: one row of one
         half-sweep each (K7, als_fold_in), x = (sum y y^T + reg n I)^-1 sum r y over the
         row's ratings against the fixed other side (the implicit form with YtY when
@@ -1326,22 +1397,26 @@ class ALSCore:
         Returns (keys [m] = the distinct ids ascending, X f32 [m, rank], n_used int32 [m] =
         ratings used per row) on the device; a row whose every rating was skipped is zero
         with n_used 0.  Works on a from_factors core.  Raises RuntimeError when a row's
-        normal equations are not positive definite (reg = 0 with fewer ratings than rank)."""
+        normal equations are not positive definite (reg = 0 with fewer ratings than rank).
+        nonnegative: the row is the minimiser under x >= 0 instead (K13, Spark's NNLS solver:
+        what a half-sweep of fit(nonnegative=True) computes for it); no row fails."""
         keys, X, n_used, _, _ = self._fold_in(ids, other_ids, ratings, float(reg), bool(implicit),
-                                              float(alpha), bool(user_side))
+                                              float(alpha), bool(user_side), bool(nonnegative))
         return keys, X[:, :self.rank], n_used
 
     def recommend_new(self, ids, other_ids, ratings, top: int, *, reg, implicit=False, alpha=1.0,
-                      user_side: bool = True, exclude_rated: bool = True, candidates=None):
+                      user_side: bool = True, exclude_rated: bool = True, candidates=None,
+                      nonnegative: bool = False):
         """fold_in, then the `top` best rows of the other side for each folded row (K5 with
         the folded rows as the query matrix): (keys [m], ids [m, t], scores [m, t]) as
         recommend_subset returns them, t = min(top, rows of the other side).
         exclude_rated: a new row never lists what it rated itself (the reference's R:229
         for a user who is not in the model); candidates: ids of the other side the lists
-        are restricted to (R:245).  Rows without a single used rating are dropped."""
+        are restricted to (R:245).  Rows without a single used rating are dropped.
+        nonnegative: as fold_in."""
         keys, X, n_used, row_ptr, col = self._fold_in(ids, other_ids, ratings, float(reg),
                                                       bool(implicit), float(alpha),
-                                                      bool(user_side))
+                                                      bool(user_side), bool(nonnegative))
         _, _, oi, Vo = self._sides(user_side)
         t = min(int(top), oi.n)
         keep = n_used > 0

@@ -20,7 +20,7 @@ import torch
 __all__ = ["pack_allow_bits", "exclusion_lists", "relevance_lists", "ragged_rows",
            "relevance_lists_weighted", "reject_sharded_filters", "reject_sharded_fold_in",
            "reject_sharded_regression", "reject_sharded_full_rank", "reject_sharded_explain",
-           "reject_sharded_similar"]
+           "reject_sharded_similar", "reject_sharded_nonnegative"]
 
 
 def pack_allow_bits(rows: torch.Tensor, n_v: int) -> torch.Tensor:
@@ -143,6 +143,14 @@ def reject_sharded_similar() -> None:
         "similar / similar_all are not supported by the sharded engine (ShardedALS) yet: "
         "search neighbours on a single-GPU ALSCore (e.g. ALSCore.from_factors over the "
         "gathered factors)")
+
+
+def reject_sharded_nonnegative() -> None:
+    """The sharded engine carries fit's nonnegative flag with the single-GPU signature and
+    refuses it, as it refuses the filters and fold-in."""
+    raise NotImplementedError(
+        "nonnegative=True (the NNLS solver, K13) is not supported by the sharded engine "
+        "(ShardedALS) yet: fit nonnegative factors on a single-GPU ALSCore")
 
 
 def reject_sharded_regression() -> None:

@@ -24,6 +24,7 @@ __all__ = ["ALS", "ALSModel"]
 
 _DEFAULT_SEED = zlib.crc32(b"org.apache.spark.ml.recommendation.ALS")
 _COLD = ("nan", "drop")
+_SOLVERS = ("cholesky", "nnls")
 
 
 def _validate(p: dict) -> None:
@@ -46,7 +47,9 @@ def _validate(p: dict) -> None:
     if p["rank"] > 128:
         raise NotImplementedError("rank > 128 is not supported by this build of the HIP kernels")
     if p["nonnegative"]:
-        raise NotImplementedError("nonnegative=True (NNLS solver) is out of scope for this build")
+        raise NotImplementedError(
+            "the Spark parameter nonnegative=True is not wired to the NNLS solver yet: use "
+            "ALS.setSolver(\"nnls\") (K13), which fits the same nonnegative model")
 
 
 class _Params:
@@ -100,6 +103,22 @@ class ALS(_Params):
         self._checkpoint_dir = None
         self._objective_every = 0
         self._objective_tol = None
+        self._solver = "cholesky"
+
+    def setSolver(self, value):
+        """The per-row solver of every half-sweep: "cholesky" (the default, Spark's
+        CholeskySolver) or "nnls" — Spark's NNLSSolver, what `nonnegative=True` selects in
+        Spark: every factor of the fitted model is >= 0 (K13).  Not a Spark Param: it is not
+        saved with the model nor enumerated by the tuners, and copy() carries it over.  The
+        fitted model's `solver` records it, and the model's fold-in methods follow it.  Not
+        together with a checkpoint directory (a checkpoint does not record the solver)."""
+        if value not in _SOLVERS:
+            raise ValueError(f"solver must be one of {_SOLVERS}, got {value!r}")
+        self._solver = value
+        return self
+
+    def getSolver(self) -> str:
+        return self._solver
 
     def setCheckpointDir(self, path):
         """Directory for factor checkpoints (None disables)."""
@@ -136,13 +155,14 @@ class ALS(_Params):
         return self
 
     def copy(self, extra=None) -> "ALS":
-        """A new estimator with the same params, checkpoint directory and objective-history
-        setting; `extra` (a param map: Param objects or names -> values) is applied to the
+        """A new estimator with the same params, checkpoint directory, solver and
+        objective-history setting; `extra` (a param map: Param objects or names -> values) is applied to the
         copy."""
         other = ALS(**self._p)
         other._checkpoint_dir = self._checkpoint_dir
         other._objective_every = self._objective_every
         other._objective_tol = self._objective_tol
+        other._solver = self._solver
         for key, value in self._param_map(extra).items():
             other._p[key] = value
         return other
@@ -184,6 +204,8 @@ class ALS(_Params):
         observe = {}
         if self._objective_every or self._objective_tol is not None:
             observe = dict(objective_every=self._objective_every, tol=self._objective_tol)
+        if self._solver == "nnls":
+            observe["nonnegative"] = True
         core.fit(int(p["rank"]), int(p["maxIter"]), float(p["regParam"]),
                  bool(p["implicitPrefs"]), float(p["alpha"]), seed=seed,
                  checkpoint_dir=self._checkpoint_dir if checkpoints else None,
@@ -200,7 +222,7 @@ class ALS(_Params):
             return self.copy(params).fit(dataset)
         _validate(self._p)
         core = _engine.make_engine(*self._columns(dataset))
-        return ALSModel(self._fit_core(core), dict(self._p))
+        return ALSModel(self._fit_core(core), dict(self._p), solver=self._solver)
 
 
 _make_accessors(ALS, list(_Params._defaults))
@@ -212,9 +234,10 @@ del _name
 class ALSModel:
     """Fitted factors resident in HBM; mirrors pyspark.ml.recommendation.ALSModel."""
 
-    def __init__(self, core: "_engine.ALSCore", params: dict):
+    def __init__(self, core: "_engine.ALSCore", params: dict, solver: str = "cholesky"):
         self._core = core
         self._p = params
+        self._solver = solver
         # the fit's (iteration, objective) pairs, copied: a tuner refits the same core
         self._objective_history = list(getattr(core, "objective_history", ()))
 
@@ -249,6 +272,15 @@ class ALSModel:
     @property
     def engine(self) -> "_engine.ALSCore":
         return self._core
+
+    @property
+    def solver(self) -> str:
+        """The per-row solver the model was fitted with (ALS.setSolver): "cholesky" or
+        "nnls".  It is not saved: a loaded model says "cholesky"."""
+        return self._solver
+
+    def _nonnegative(self, nonnegative) -> bool:
+        return self._solver == "nnls" if nonnegative is None else bool(nonnegative)
 
     @property
     def objectiveHistory(self):
@@ -455,30 +487,37 @@ class ALSModel:
                                            implicit=bool(p["implicitPrefs"]),
                                            alpha=float(p["alpha"]), user_side=user_side)
 
-    def _fold_in_df(self, dataset, user_side: bool):
+    def _fold_in_df(self, dataset, user_side: bool, nonnegative=None):
         args, kw = self._fold_args(dataset, user_side)
+        if self._nonnegative(nonnegative):
+            kw["nonnegative"] = True
         keys, X, _ = self._core.fold_in(*args, **kw)
         return self._factors_df(keys, X)
 
-    def foldInUsers(self, dataset):
+    def foldInUsers(self, dataset, nonnegative=None):
         """Factors for users that are not in the model, from their ratings alone and
         without a refit: DataFrame[id, features], one row per distinct user of `dataset`
         (userCol, itemCol, ratingCol), each solved against the fixed item factors with
         the model's regParam / implicitPrefs / alpha — one row of one ALS half-sweep.
-        Items the model does not know are skipped; the model itself is not changed."""
-        return self._fold_in_df(dataset, True)
+        Items the model does not know are skipped; the model itself is not changed.
+        nonnegative: solve each row under x >= 0 (K13); None = as the model was fitted
+        (`solver`), False for a loaded model."""
+        return self._fold_in_df(dataset, True, nonnegative)
 
-    def foldInItems(self, dataset):
+    def foldInItems(self, dataset, nonnegative=None):
         """foldInUsers for new items against the fixed user factors."""
-        return self._fold_in_df(dataset, False)
+        return self._fold_in_df(dataset, False, nonnegative)
 
     def recommendForNewUsers(self, dataset, numItems: int, *, excludeRated: bool = True,
-                             candidates=None):
+                             candidates=None, nonnegative=None):
         """Top items for users that are not in the model (foldInUsers, then K5 over the
         folded rows), in recommendForUserSubset's form.  excludeRated: a user's own rated
         items are left out of their list; candidates: item ids the lists are restricted
-        to.  Users without a single rating of a known item are absent."""
+        to.  Users without a single rating of a known item are absent.  nonnegative: as
+        foldInUsers."""
         args, kw = self._fold_args(dataset, True)
+        if self._nonnegative(nonnegative):
+            kw["nonnegative"] = True
         if candidates is not None:
             candidates = check_integers(np.asarray(candidates).reshape(-1), self._p["itemCol"])
         return self._recs_df(self._p["userCol"], *self._core.recommend_new(

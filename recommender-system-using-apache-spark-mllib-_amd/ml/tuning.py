@@ -138,12 +138,13 @@ def _fit_and_score(estimator, maps, evaluator, train, validation, collect: bool)
         if core is None or cols != built_for:
             core, built_for = _engine.make_engine(*est._columns(train)), cols
         est._fit_core(core, checkpoints=False)
-        model = ALSModel(core, dict(est._p))
+        model = ALSModel(core, dict(est._p), solver=est.getSolver())
         metrics.append(_score(evaluator, model, validation))   # before the next fit
         if collect:  # the shared engine's factors are overwritten by the next fit
             uids, U = core.user_factors()
             iids, V = core.item_factors()
-            subs.append(ALSModel(_engine.ALSCore.from_factors(uids, U, iids, V), dict(est._p)))
+            subs.append(ALSModel(_engine.ALSCore.from_factors(uids, U, iids, V), dict(est._p),
+                                 solver=est.getSolver()))
     return metrics, subs
 
 

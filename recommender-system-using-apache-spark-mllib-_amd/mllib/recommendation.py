@@ -218,34 +218,39 @@ class MatrixFactorizationModel:
                 for k, ri, rs in zip(keys, ids, sc)]
 
     def foldInUsers(self, ratings, lambda_: float, *, implicit: bool = False,
-                    alpha: float = 0.01):
+                    alpha: float = 0.01, nonnegative: bool = False):
         """Factors for users that are not in the model, from their (user, product,
         rating) triples alone and without a refit: [(user, array)] in ascending user
         order, each solved against the fixed product factors (one row of one ALS
         half-sweep, K7).  lambda_ (and implicit / alpha, as in trainImplicit) are
         arguments because this model stores no training parameters.  Products the model
-        does not know are skipped; the model itself is not changed."""
+        does not know are skipped; the model itself is not changed.  nonnegative: solve
+        each row under x >= 0 (K13), as ALS.trainNonnegative does."""
         _check(self.rank, 0, lambda_, False, alpha)
         u, i, r = _triples(ratings)
+        extra = dict(nonnegative=True) if nonnegative else {}
         keys, X, _ = self._core.fold_in(u, i, r, reg=float(lambda_), implicit=bool(implicit),
-                                        alpha=float(alpha))
+                                        alpha=float(alpha), **extra)
         X = X.double().cpu().numpy()
         return [(int(a), row) for a, row in zip(keys.cpu().numpy(), X)]
 
     def recommendProductsForNewUsers(self, ratings, num: int, lambda_: float, *,
                                      implicit: bool = False, alpha: float = 0.01,
-                                     exclude_rated: bool = True, candidates=None):
+                                     exclude_rated: bool = True, candidates=None,
+                                     nonnegative: bool = False):
         """Top `num` products for users that are not in the model (foldInUsers, then K5):
         [(user, [Rating])] as recommendProductsForUsers returns.  exclude_rated: a user's
         own rated products are left out; candidates: product ids the lists are restricted
-        to.  Users without a single rating of a known product are absent."""
+        to.  Users without a single rating of a known product are absent.  nonnegative: as
+        foldInUsers."""
         _check(self.rank, 0, lambda_, False, alpha)
         u, i, r = _triples(ratings)
         if candidates is not None:
             candidates = check_integers(np.asarray(candidates).reshape(-1), "product")
+        extra = dict(nonnegative=True) if nonnegative else {}
         keys, ids, sc = self._core.recommend_new(
             u, i, r, int(num), reg=float(lambda_), implicit=bool(implicit), alpha=float(alpha),
-            exclude_rated=bool(exclude_rated), candidates=candidates)
+            exclude_rated=bool(exclude_rated), candidates=candidates, **extra)
         keys, ids, sc = keys.cpu().numpy(), ids.cpu().numpy(), sc.cpu().numpy()
         return [(int(k), [Rating(int(k), int(a), float(s)) for a, s in zip(ri, rs)
                           if np.isfinite(s)])
@@ -312,7 +317,9 @@ def _check(rank, iterations, lambda_, nonnegative, alpha=0.0):
     if alpha < 0:
         raise ValueError(f"alpha must be >= 0, got {alpha}")
     if nonnegative:
-        raise NotImplementedError("nonnegative=True (NNLS solver) is out of scope for this build")
+        raise NotImplementedError(
+            "the Spark parameter nonnegative=True is not wired to the NNLS solver yet: use "
+            "ALS.trainNonnegative (K13), which trains the same nonnegative model")
 
 
 class ALS:
@@ -338,6 +345,22 @@ class ALS:
         core = _engine.make_engine(u, i, r)
         core.fit(int(rank), int(iterations), float(lambda_), True, float(alpha),
                  seed=_DEFAULT_SEED if seed is None else int(seed))
+        return MatrixFactorizationModel(core)
+
+
+    @classmethod
+    def trainNonnegative(cls, ratings, rank: int, iterations: int = 5, lambda_: float = 0.01,
+                         seed: Optional[int] = None, implicitPrefs: bool = False,
+                         alpha: float = 0.01) -> MatrixFactorizationModel:
+        """train / trainImplicit with Spark's NNLSSolver in place of CholeskySolver — what
+        `nonnegative=True` selects in Spark: every factor of the model is >= 0 (K13).  Not a
+        pyspark method: the Spark spelling train(nonnegative=True) still raises."""
+        _check(rank, iterations, lambda_, False, alpha)
+        u, i, r = _triples(ratings)
+        core = _engine.make_engine(u, i, r)
+        core.fit(int(rank), int(iterations), float(lambda_), bool(implicitPrefs),
+                 float(alpha) if implicitPrefs else 1.0,
+                 seed=_DEFAULT_SEED if seed is None else int(seed), nonnegative=True)
         return MatrixFactorizationModel(core)
 
 
