@@ -6,8 +6,7 @@
 //   score(u, t) = y_t^T A_u^-1 b_u = sum_j wb_j (z_t . y_j),   z_t = A_u^-1 y_t.
 // K7 (fold_in.hip) forms and factors the same A_u but keeps only x_u; this kernel keeps the
 // factor in LDS and solves against the targets instead.  The gather / Gram / LDL^T device
-// code is K7's, copied (fold_in.hip stays as it is; DESIGN.md section K11 lists the
-// duplication as a clean-up), minus b, which is not needed here.
+// code is shared with K7 through row_system.h, minus b, which is not needed here.
 //
 // One 256-thread workgroup per row, one launch, no workspace:
 //   pass 1   K7's gather + Gram + square-root-free LDL^T: the lower-packed fp64 triangle
@@ -24,17 +23,12 @@
 // Everything a result depends on runs in a fixed order: two calls give the same bits.
 #include <algorithm>
 
-#include "als_common.h"
+#include "row_system.h"
 
 namespace als {
 
-constexpr int kExMaxRank = 128;
-constexpr int kExThreads = 256;
-constexpr int kExBatch = 32;         // ratings gathered per step
 constexpr int kExTargets = 16;       // targets solved per step: one 16-lane group each
 constexpr int kExMaxTop = 32;
-constexpr int kExMaxBlocks = 65536;  // blocks stride over the rows past this
-constexpr double kExPivotEps = 0x1p-46;  // K7's pivot rule (kFiPivotEps)
 
 // Dynamic LDS of one block, byte offsets (all 16-byte multiples).  Unlike K7 the gather
 // buffer cannot alias the triangle: pass 3 gathers while the factor is still needed.
@@ -47,15 +41,15 @@ __host__ __device__ static inline ExLds ex_lds(int k, int kp) {
   ExLds l;
   int off = (k * (k + 1) / 2 * 8 + 15) / 16 * 16;          // the packed triangle, k rows
   l.z = off;    off += kExTargets * (kp + 2) * 8;          // z_t per target
-  l.sc = off;   off += kExTargets * kExBatch * 8;          // the batch's contributions
+  l.sc = off;   off += kExTargets * kRowBatch * 8;          // the batch's contributions
   l.lc = off;   off += kExTargets * kExMaxTop * 8;         // list values, sorted
-  l.diag = off; off += kExMaxRank * 8;                     // diagonal of A as summed
-  l.inv = off;  off += kExMaxRank * 8;                     // 1 / d_j
-  l.wa = off;   off += kExBatch * 8;
-  l.wb = off;   off += kExBatch * 8;
-  l.ybuf = off; off += kExBatch * (kp + 4) * 4;            // gathered factor rows
+  l.diag = off; off += kRowMaxRank * 8;                     // diagonal of A as summed
+  l.inv = off;  off += kRowMaxRank * 8;                     // 1 / d_j
+  l.wa = off;   off += kRowBatch * 8;
+  l.wb = off;   off += kRowBatch * 8;
+  l.ybuf = off; off += kRowBatch * (kp + 4) * 4;            // gathered factor rows
   l.lp = off;   off += kExTargets * kExMaxTop * 4;         // list entry positions
-  l.col = off;  off += kExBatch * 4;
+  l.col = off;  off += kRowBatch * 4;
   l.cnt = off;  off += 16;
   l.total = off;
   return l;
@@ -68,66 +62,9 @@ __device__ __forceinline__ double ex_shfl16(double v, int src) {  // inside a 16
   return __builtin_bit_cast(double, iv);
 }
 
-// Wave 0: ids and weights of the batch starting at s0 (K7's rules); counts the used ones.
-template <bool IMPLICIT>
-__device__ __forceinline__ void ex_weights(int64_t s0, int64_t pe, const int32_t* __restrict__ col,
-                                           const float* __restrict__ val, int64_t n_src,
-                                           float alpha, int lane, int* scol, double* swa,
-                                           double* swb, int& n_used, int& n_pos) {
-  bool used = false, pos = false;
-  if (lane < kExBatch) {
-    const int64_t s = s0 + lane;
-    int c = -1;
-    double wa = 0.0, wb = 0.0;
-    if (s < pe) {
-      c = col[s];
-      const double r = (double)val[s];
-      used = c >= 0 && (int64_t)c < n_src;
-      if (used) {
-        pos = r > 0.0;
-        if (IMPLICIT) {
-          const double c1 = (double)alpha * fabs(r);
-          wa = c1;
-          wb = pos ? 1.0 + c1 : 0.0;
-        } else {
-          wa = 1.0;
-          wb = r;
-        }
-      } else {
-        c = -1;
-      }
-    }
-    scol[lane] = c;
-    swa[lane] = wa;
-    swb[lane] = wb;
-  }
-  n_used += __popcll(__ballot(used));
-  n_pos += __popcll(__ballot(pos));
-}
-
-// All threads: the batch's factor rows into LDS as float4 pieces, columns >= k (padding,
-// whatever it holds) and unknown items as zeros.
-template <int KP>
-__device__ __forceinline__ void ex_gather(const float* __restrict__ Y, int ld, int k,
-                                          const int* scol, float* ybuf, int t) {
-  constexpr int P4 = KP / 4, YS = KP + 4;
-  for (int g = t; g < kExBatch * P4; g += kExThreads) {
-    const int e = g / P4, c0 = (g % P4) * 4;
-    const int c = scol[e];
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c >= 0 && c0 < k) {  // c0 < k <= ld and ld % 4 == 0: the piece lies inside the row
-      v = *reinterpret_cast<const float4*>(Y + (int64_t)c * ld + c0);
-      if (c0 + 1 >= k) v.y = 0.f;
-      if (c0 + 2 >= k) v.z = 0.f;
-      if (c0 + 3 >= k) v.w = 0.f;
-    }
-    *reinterpret_cast<float4*>(ybuf + e * YS + c0) = v;
-  }
-}
-
 // NB = k_pad / 16: thread (a, b) owns rows a + 16 p and columns b + 16 q, q <= p < NB.
 template <int NB, bool IMPLICIT>
-__global__ __launch_bounds__(kExThreads) void explain_kernel(
+__global__ __launch_bounds__(kRowThreads) void explain_kernel(
     const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
     const float* __restrict__ val, int64_t n_rows, const float* __restrict__ Y, int64_t n_src,
     int ld, int k, float reg, float alpha, const double* __restrict__ yty,
@@ -162,35 +99,21 @@ __global__ __launch_bounds__(kExThreads) void explain_kernel(
     const int64_t qb = tgt_ptr[row], qe = tgt_ptr[row + 1];
     const bool work = qe > qb;  // a row without targets is counted, not factored
 
-    // ---- pass 1: gather + Gram (K7)
+    // ---- pass 1: gather + Gram (row_system.h)
     double acc[NACC];
 #pragma unroll
     for (int i = 0; i < NACC; ++i) acc[i] = 0.0;
+    double no_b = 0.0;          // WITH_B = false: b is not summed
     int n_used = 0, n_pos = 0;  // wave 0 only
-    for (int64_t s0 = pb; s0 < pe; s0 += kExBatch) {
+    for (int64_t s0 = pb; s0 < pe; s0 += kRowBatch) {
       if (t < 64)
-        ex_weights<IMPLICIT>(s0, pe, col, val, n_src, alpha, lane, scol, swa, swb, n_used, n_pos);
+        row_weights<IMPLICIT>(s0, pe, col, val, n_src, alpha, lane, scol, swa, swb, n_used, n_pos);
       __syncthreads();
       if (work) {
-        ex_gather<KP>(Y, ld, k, scol, ybuf, t);
+        row_gather<KP, YS>(Y, ld, k, scol, ybuf, t);
         __syncthreads();
-        const int nb = pe - s0 < kExBatch ? (int)(pe - s0) : kExBatch;
-        for (int e = 0; e < nb; ++e) {
-          const float* ye = ybuf + e * YS;
-          const double wa = swa[e];
-          double yj[NB], wyi[NB];
-#pragma unroll
-          for (int p = 0; p < NB; ++p) {
-            wyi[p] = wa * (double)ye[ta + 16 * p];
-            yj[p] = (double)ye[tb + 16 * p];
-          }
-#pragma unroll
-          for (int p = 0; p < NB; ++p) {
-#pragma unroll
-            for (int q = 0; q <= p; ++q)
-              acc[p * (p + 1) / 2 + q] = fma(wyi[p], yj[q], acc[p * (p + 1) / 2 + q]);
-          }
-        }
+        const int nb = pe - s0 < kRowBatch ? (int)(pe - s0) : kRowBatch;
+        row_gram_batch<NB, YS, false>(ybuf, nb, swa, swb, acc, no_b);
       }
       __syncthreads();  // the next batch overwrites scol and ybuf
     }
@@ -207,7 +130,6 @@ __global__ __launch_bounds__(kExThreads) void explain_kernel(
 
     bool ok = n_all > 0;  // no used entry: zero scores and empty lists, not an error
     if (ok) {
-      // accumulators -> the packed triangle
 #pragma unroll
       for (int p = 0; p < NB; ++p) {
 #pragma unroll
@@ -226,31 +148,16 @@ __global__ __launch_bounds__(kExThreads) void explain_kernel(
         }
       }
       __syncthreads();
-      // LDL^T, right-looking, column j left as l_ij d_j.  A pivot counts as positive only
-      // above kExPivotEps of its diagonal entry of A (K7's rule).
-      for (int j = 0; j < k; ++j) {
-        const double d = Ap[j * (j + 1) / 2 + j];
-        if (!(d > kExPivotEps * sdiag[j])) {  // the same words for every thread: a uniform exit
-          ok = false;
-          break;
-        }
-        const double inv_d = 1.0 / d;
-        for (int i = j + 1 + ta; i < k; i += 16) {
-          const double cij = Ap[i * (i + 1) / 2 + j] * inv_d;
-          for (int l = j + 1 + tb; l <= i; l += 16)
-            Ap[i * (i + 1) / 2 + l] = fma(-cij, Ap[l * (l + 1) / 2 + j], Ap[i * (i + 1) / 2 + l]);
-        }
-        __syncthreads();
-      }
+      ok = row_ldlt<false>(Ap, sdiag, k);
       if (!ok && t == 0) atomicCAS(status, 0, (int32_t)(row + 1));
     }
     if (!ok) {  // uniform: the row's slots read as "nothing to explain"
       const int64_t n_out = (qe - qb) * top_n;
-      for (int64_t i = t; i < n_out; i += kExThreads) {
+      for (int64_t i = t; i < n_out; i += kRowThreads) {
         pos_out[qb * top_n + i] = -1;
         contrib_out[qb * top_n + i] = 0.f;
       }
-      for (int64_t i = qb + t; i < qe; i += kExThreads) score_out[i] = 0.f;
+      for (int64_t i = qb + t; i < qe; i += kRowThreads) score_out[i] = 0.f;
       __syncthreads();
       continue;
     }
@@ -311,13 +218,13 @@ __global__ __launch_bounds__(kExThreads) void explain_kernel(
       double score = 0.0;  // lane 0 of the group
       int n_list = 0;
       const int k4 = (k + 3) & ~3;
-      for (int64_t s0 = pb; s0 < pe; s0 += kExBatch) {
+      for (int64_t s0 = pb; s0 < pe; s0 += kRowBatch) {
         if (t < 64) {
           int u0 = 0, u1 = 0;
-          ex_weights<IMPLICIT>(s0, pe, col, val, n_src, alpha, lane, scol, swa, swb, u0, u1);
+          row_weights<IMPLICIT>(s0, pe, col, val, n_src, alpha, lane, scol, swa, swb, u0, u1);
         }
         __syncthreads();
-        ex_gather<KP>(Y, ld, k, scol, ybuf, t);
+        row_gather<KP, YS>(Y, ld, k, scol, ybuf, t);
         __syncthreads();
         if (known) {
           const double* zt = sz + ta * ZS;
@@ -339,17 +246,17 @@ __global__ __launch_bounds__(kExThreads) void explain_kernel(
           }
           // the dot first, then the weight: equal items with equal ratings tie bit for bit;
           // + 0.0 turns the -0 of a zero weight into +0
-          sc[ta * kExBatch + tb] = swb[tb] * d0 + 0.0;
-          sc[ta * kExBatch + tb + 16] = swb[tb + 16] * d1 + 0.0;
+          sc[ta * kRowBatch + tb] = swb[tb] * d0 + 0.0;
+          sc[ta * kRowBatch + tb + 16] = swb[tb + 16] * d1 + 0.0;
         }
         __syncthreads();
         if (known && tb == 0) {
-          const int nb = pe - s0 < kExBatch ? (int)(pe - s0) : kExBatch;
+          const int nb = pe - s0 < kRowBatch ? (int)(pe - s0) : kRowBatch;
           double* const vc = lc + ta * kExMaxTop;
           int* const vp = lp + ta * kExMaxTop;
           for (int e = 0; e < nb; ++e) {
             if (scol[e] < 0) continue;  // not a used entry: no candidate
-            const double c = sc[ta * kExBatch + e];
+            const double c = sc[ta * kRowBatch + e];
             score += c;                 // every contribution, in row order
             // entries come in ascending position: an equal value goes behind
             if (n_list == top_n && !(c > vc[top_n - 1])) continue;
@@ -400,54 +307,30 @@ int als_explain(const int64_t* row_ptr, const int32_t* col, const float* val, in
                 void* stream) {
   (void)ws;
   (void)ws_bytes;
-  ALS_REQUIRE(k >= 1 && k <= kExMaxRank, ALS_EUNSUPPORTED, "als_explain: rank %d not in [1, %d]",
-              k, kExMaxRank);
+  if (int rc = row_check_args("als_explain", k, ld, n_rows, n_src, reg, alpha, implicit,
+                              yty_packed))
+    return rc;
   ALS_REQUIRE(top_n >= 1 && top_n <= kExMaxTop, ALS_EUNSUPPORTED,
               "als_explain: top_n %d not in [1, %d]", top_n, kExMaxTop);
-  ALS_REQUIRE(ld >= k && ld % 4 == 0, ALS_EINVAL,
-              "als_explain: ld %d must be >= k and a multiple of 4", ld);
-  ALS_REQUIRE(n_rows >= 0 && n_rows < (int64_t(1) << 31) - 1, ALS_EINVAL,
-              "als_explain: n_rows outside [0, 2^31 - 1)");
-  ALS_REQUIRE(n_src >= 0 && n_src < (int64_t(1) << 31), ALS_EINVAL,
-              "als_explain: n_src outside [0, 2^31)");
-  ALS_REQUIRE(reg >= 0.f && alpha >= 0.f, ALS_EINVAL, "als_explain: reg/alpha must be >= 0");
-  ALS_REQUIRE(!implicit || yty_packed, ALS_EINVAL, "als_explain: implicit needs yty_packed");
   if (n_rows == 0) return ALS_OK;
   ALS_REQUIRE(row_ptr && col && val && tgt_ptr && tgt && score && contrib_pos && contrib &&
                   status_dev,
               ALS_EINVAL, "als_explain: null pointer");
-  ALS_REQUIRE(n_src == 0 || Y_src, ALS_EINVAL, "als_explain: null Y_src");
-  ALS_REQUIRE((reinterpret_cast<uintptr_t>(Y_src) & 15) == 0, ALS_EINVAL,
-              "als_explain: Y_src not 16-byte aligned");
+  if (int rc = row_check_source("als_explain", n_src, Y_src, nullptr)) return rc;
   hipStream_t st = as_stream(stream);
   const int nb = als_k_pad(k) / 16;
   const int lds = ex_lds(k, 16 * nb).total;
-  const unsigned grid = (unsigned)std::min<int64_t>(n_rows, kExMaxBlocks);
-#define ALS_EX_LAUNCH(NB, IMP)                                                                  \
-  do {                                                                                          \
-    ALS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&explain_kernel<NB, IMP>),        \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));              \
-    explain_kernel<NB, IMP><<<grid, kExThreads, lds, st>>>(                                     \
-        row_ptr, col, val, n_rows, Y_src, n_src, ld, k, reg, alpha, yty_packed, tgt_ptr, tgt,   \
-        top_n, score, contrib_pos, contrib, n_used_out, status_dev);                            \
-  } while (0)
-#define ALS_EX_MODE(NB)            \
-  do {                             \
-    if (implicit)                  \
-      ALS_EX_LAUNCH(NB, true);     \
-    else                           \
-      ALS_EX_LAUNCH(NB, false);    \
-  } while (0)
-  switch (nb) {
-    case 1: ALS_EX_MODE(1); break;
-    case 2: ALS_EX_MODE(2); break;
-    case 4: ALS_EX_MODE(4); break;
-    default: ALS_EX_MODE(8); break;
-  }
-#undef ALS_EX_MODE
-#undef ALS_EX_LAUNCH
-  ALS_LAUNCH_CHECK();
-  return ALS_OK;
+  const unsigned grid = (unsigned)std::min<int64_t>(n_rows, kRowMaxBlocks);
+  return row_dispatch(nb, implicit, [&](auto nbc, auto imp) -> int {
+    constexpr auto kernel = &explain_kernel<decltype(nbc)::value, decltype(imp)::value>;
+    ALS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    kernel<<<grid, kRowThreads, lds, st>>>(row_ptr, col, val, n_rows, Y_src, n_src, ld, k, reg,
+                                           alpha, yty_packed, tgt_ptr, tgt, top_n, score,
+                                           contrib_pos, contrib, n_used_out, status_dev);
+    ALS_LAUNCH_CHECK();
+    return ALS_OK;
+  });
 }
 
 }  // extern "C"

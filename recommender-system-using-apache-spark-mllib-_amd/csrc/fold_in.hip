@@ -8,7 +8,8 @@
 // als_solve_half is the wrong tool for it: it needs a CSR schedule (three host syncs), its
 // explicit PREP re-splits all of Y_src, and a serving-only core has no rating blocks.
 //
-// One 256-thread workgroup per row, one launch, no workspace, no pass over Y_src:
+// One 256-thread workgroup per row, one launch, no workspace, no pass over Y_src.  The
+// gather, the Gram and the factorisation are row_system.h's, shared with K11 and K13:
 //   gather   The row's ratings are taken 32 at a time.  Wave 0 reads (col, val) of the
 //            batch, turns them into the weights of the two sums and counts the used ones;
 //            then all four waves copy the 32 factor rows into LDS as float4 pieces,
@@ -27,15 +28,9 @@
 // A long row runs the same gather/gram loop serially; there is no chunked path.
 #include <algorithm>
 
-#include "als_common.h"
+#include "row_system.h"
 
 namespace als {
-
-constexpr int kFiMaxRank = 128;
-constexpr int kFiThreads = 256;
-constexpr int kFiBatch = 32;         // ratings gathered per step
-constexpr int kFiMaxBlocks = 65536;  // blocks stride over the rows past this
-constexpr double kFiPivotEps = 0x1p-46;  // kFiMaxRank * 2^-53: see the factor step
 
 // Dynamic LDS of one block.  The packed triangle comes first; the gather buffer aliases
 // its head (it is dead when the accumulators are written out) when the triangle is the
@@ -50,16 +45,16 @@ __host__ __device__ static inline FiLds fi_lds(int k, int kp) {
   FiLds l;
   l.tri_doubles = (k + 1) * (k + 2) / 2;
   const int tri = (l.tri_doubles * 8 + 15) / 16 * 16;
-  const int ybuf = kFiBatch * kp * 4;
+  const int ybuf = kRowBatch * kp * 4;
   l.head_bytes = tri > ybuf ? tri : ybuf;
-  // + x broadcast (kMaxRank doubles) + two weights per batch slot + col per slot + 4 ints
-  l.total_bytes = l.head_bytes + kFiMaxRank * 8 + 2 * kFiBatch * 8 + kFiBatch * 4 + 16;
+  // + x broadcast (kRowMaxRank doubles) + two weights per batch slot + col per slot + 4 ints
+  l.total_bytes = l.head_bytes + kRowMaxRank * 8 + 2 * kRowBatch * 8 + kRowBatch * 4 + 16;
   return l;
 }
 
 // NB = k_pad / 16: thread (a, b) owns rows a + 16 p and columns b + 16 q, q <= p < NB.
 template <int NB, bool IMPLICIT>
-__global__ __launch_bounds__(kFiThreads) void fold_in_kernel(
+__global__ __launch_bounds__(kRowThreads) void fold_in_kernel(
     const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
     const float* __restrict__ val, int64_t n_rows, const float* __restrict__ Y, int64_t n_src,
     int ld, int k, float reg, float alpha, const double* __restrict__ yty,
@@ -67,17 +62,15 @@ __global__ __launch_bounds__(kFiThreads) void fold_in_kernel(
     int32_t* __restrict__ status) {
   constexpr int KP = 16 * NB;
   constexpr int NACC = NB * (NB + 1) / 2;
-  constexpr int P4 = KP / 4;                   // float4 pieces per gathered row
-  constexpr int PIECES = kFiBatch * P4;        // per batch
   extern __shared__ float4 fi_smem[];  // 16-byte aligned
   const FiLds L = fi_lds(k, KP);
   double* const Ap = reinterpret_cast<double*>(fi_smem);        // packed triangle
-  float* const ybuf = reinterpret_cast<float*>(fi_smem);        // [kFiBatch][KP], aliases Ap
+  float* const ybuf = reinterpret_cast<float*>(fi_smem);        // [kRowBatch][KP], aliases Ap
   double* const sx = reinterpret_cast<double*>(reinterpret_cast<char*>(fi_smem) + L.head_bytes);
-  double* const swa = sx + kFiMaxRank;   // weight of y y^T per batch slot
-  double* const swb = swa + kFiBatch;    // weight of y in b
-  int* const scol = reinterpret_cast<int*>(swb + kFiBatch);
-  int* const scnt = scol + kFiBatch;     // [0] used entries, [1] used entries with r > 0
+  double* const swa = sx + kRowMaxRank;   // weight of y y^T per batch slot
+  double* const swb = swa + kRowBatch;    // weight of y in b
+  int* const scol = reinterpret_cast<int*>(swb + kRowBatch);
+  int* const scnt = scol + kRowBatch;     // [0] used entries, [1] used entries with r > 0
 
   const int t = threadIdx.x;
   const int ta = t >> 4, tb = t & 15;
@@ -90,71 +83,14 @@ __global__ __launch_bounds__(kFiThreads) void fold_in_kernel(
     for (int i = 0; i < NACC; ++i) acc[i] = 0.0;
     double bacc = 0.0;
     int n_used = 0, n_pos = 0;  // wave 0 only
-
-    for (int64_t s0 = pb; s0 < pe; s0 += kFiBatch) {
-      if (t < 64) {  // wave 0: the batch's ids and weights
-        bool used = false, pos = false;
-        if (lane < kFiBatch) {
-          const int64_t s = s0 + lane;
-          int c = -1;
-          double wa = 0.0, wb = 0.0;
-          if (s < pe) {
-            c = col[s];
-            const double r = (double)val[s];
-            used = c >= 0 && (int64_t)c < n_src;
-            if (used) {
-              pos = r > 0.0;
-              if (IMPLICIT) {
-                const double c1 = (double)alpha * fabs(r);
-                wa = c1;
-                wb = pos ? 1.0 + c1 : 0.0;
-              } else {
-                wa = 1.0;
-                wb = r;
-              }
-            } else {
-              c = -1;
-            }
-          }
-          scol[lane] = c;
-          swa[lane] = wa;
-          swb[lane] = wb;
-        }
-        n_used += __popcll(__ballot(used));
-        n_pos += __popcll(__ballot(pos));
-      }
+    for (int64_t s0 = pb; s0 < pe; s0 += kRowBatch) {
+      if (t < 64)
+        row_weights<IMPLICIT>(s0, pe, col, val, n_src, alpha, lane, scol, swa, swb, n_used, n_pos);
       __syncthreads();
-      for (int g = t; g < PIECES; g += kFiThreads) {  // the batch's factor rows
-        const int e = g / P4, c0 = (g % P4) * 4;
-        const int c = scol[e];
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (c >= 0 && c0 < k) {  // c0 < k <= ld and ld % 4 == 0: the piece lies inside the row
-          v = *reinterpret_cast<const float4*>(Y + (int64_t)c * ld + c0);
-          if (c0 + 1 >= k) v.y = 0.f;
-          if (c0 + 2 >= k) v.z = 0.f;
-          if (c0 + 3 >= k) v.w = 0.f;
-        }
-        *reinterpret_cast<float4*>(ybuf + e * KP + c0) = v;
-      }
+      row_gather<KP, KP>(Y, ld, k, scol, ybuf, t);
       __syncthreads();
-      const int nb = pe - s0 < kFiBatch ? (int)(pe - s0) : kFiBatch;
-      for (int e = 0; e < nb; ++e) {
-        const float* ye = ybuf + e * KP;
-        const double wa = swa[e];
-        double yj[NB], wyi[NB];
-#pragma unroll
-        for (int p = 0; p < NB; ++p) {
-          wyi[p] = wa * (double)ye[ta + 16 * p];
-          yj[p] = (double)ye[tb + 16 * p];
-        }
-#pragma unroll
-        for (int p = 0; p < NB; ++p) {
-#pragma unroll
-          for (int q = 0; q <= p; ++q)
-            acc[p * (p + 1) / 2 + q] = fma(wyi[p], yj[q], acc[p * (p + 1) / 2 + q]);
-        }
-        if (t < KP) bacc = fma(swb[e], (double)ye[t], bacc);
-      }
+      const int nb = pe - s0 < kRowBatch ? (int)(pe - s0) : kRowBatch;
+      row_gram_batch<NB, KP, true>(ybuf, nb, swa, swb, acc, bacc);
       __syncthreads();  // the next batch (or the triangle) overwrites ybuf
     }
     if (t == 0) {
@@ -167,12 +103,12 @@ __global__ __launch_bounds__(kFiThreads) void fold_in_kernel(
     float* const xr = X + row * (int64_t)ld_out;
     if (n_used_out && t == 0) n_used_out[row] = n_all;
     if (n_all == 0) {  // no used entry: a zero row, not an error
-      for (int c = t; c < ld_out; c += kFiThreads) xr[c] = 0.f;
+      for (int c = t; c < ld_out; c += kRowThreads) xr[c] = 0.f;
       __syncthreads();  // scnt is rewritten by the next row
       continue;
     }
 
-    // accumulators -> the packed triangle, row k = b
+    // accumulators -> the packed triangle (its diagonal as summed in sx), row k = b
 #pragma unroll
     for (int p = 0; p < NB; ++p) {
 #pragma unroll
@@ -193,30 +129,10 @@ __global__ __launch_bounds__(kFiThreads) void fold_in_kernel(
     if (t < k) Ap[k * (k + 1) / 2 + t] = bacc;
     __syncthreads();
 
-    // LDL^T, right-looking, column j left as l_ij d_j; row k (= b) rides along, so that
-    // after column j its entry j holds (L^-1 b)_j
-    // A pivot counts as positive only above kFiPivotEps of its diagonal entry of A: below
-    // that it is rounding residue of the elimination (k * 2^-53 <= 2^-46 of a_jj), whose
-    // sign is chance, so a rank-deficient A is reported whichever way it rounded.
-    bool ok = true;
-    for (int j = 0; j < k; ++j) {
-      const double d = Ap[j * (j + 1) / 2 + j];
-      if (!(d > kFiPivotEps * sx[j])) {  // the same words for every thread: a uniform exit
-        ok = false;
-        break;
-      }
-      const double inv_d = 1.0 / d;
-      for (int i = j + 1 + ta; i <= k; i += 16) {
-        const double cij = Ap[i * (i + 1) / 2 + j] * inv_d;
-        const int lmax = i < k ? i : k - 1;
-        for (int l = j + 1 + tb; l <= lmax; l += 16)
-          Ap[i * (i + 1) / 2 + l] = fma(-cij, Ap[l * (l + 1) / 2 + j], Ap[i * (i + 1) / 2 + l]);
-      }
-      __syncthreads();
-    }
-    if (!ok) {
+    // row k (= b) rides along, so that after column j its entry j holds (L^-1 b)_j
+    if (!row_ldlt<true>(Ap, sx, k)) {
       if (t == 0) atomicCAS(status, 0, (int32_t)(row + 1));
-      for (int c = t; c < ld_out; c += kFiThreads) xr[c] = 0.f;
+      for (int c = t; c < ld_out; c += kRowThreads) xr[c] = 0.f;
       __syncthreads();
       continue;
     }
@@ -233,7 +149,7 @@ __global__ __launch_bounds__(kFiThreads) void fold_in_kernel(
       if (t < l) zi = fma(-(Ap[l * (l + 1) / 2 + t] * inv_di), sx[l], zi);
     }
     // k <= 128 < 256 threads: a column c < k is thread c's own
-    for (int c = t; c < ld_out; c += kFiThreads) xr[c] = c < k ? (float)zi : 0.f;
+    for (int c = t; c < ld_out; c += kRowThreads) xr[c] = c < k ? (float)zi : 0.f;
     __syncthreads();  // Ap, sx and scnt are rewritten by the next row
   }
 }
@@ -257,54 +173,29 @@ int als_fold_in(const int64_t* row_ptr, const int32_t* col, const float* val, in
                 void* stream) {
   (void)ws;
   (void)ws_bytes;
-  ALS_REQUIRE(k >= 1 && k <= kFiMaxRank, ALS_EUNSUPPORTED, "als_fold_in: rank %d not in [1, %d]",
-              k, kFiMaxRank);
-  ALS_REQUIRE(ld >= k && ld % 4 == 0, ALS_EINVAL,
-              "als_fold_in: ld %d must be >= k and a multiple of 4", ld);
+  if (int rc = row_check_args("als_fold_in", k, ld, n_rows, n_src, reg, alpha, implicit,
+                              yty_packed))
+    return rc;
   ALS_REQUIRE(ld_out >= k && ld_out % 4 == 0, ALS_EINVAL,
               "als_fold_in: ld_out %d must be >= k and a multiple of 4", ld_out);
-  ALS_REQUIRE(n_rows >= 0 && n_rows < (int64_t(1) << 31) - 1, ALS_EINVAL,
-              "als_fold_in: n_rows outside [0, 2^31 - 1)");
-  ALS_REQUIRE(n_src >= 0 && n_src < (int64_t(1) << 31), ALS_EINVAL,
-              "als_fold_in: n_src outside [0, 2^31)");
-  ALS_REQUIRE(reg >= 0.f && alpha >= 0.f, ALS_EINVAL, "als_fold_in: reg/alpha must be >= 0");
-  ALS_REQUIRE(!implicit || yty_packed, ALS_EINVAL, "als_fold_in: implicit needs yty_packed");
   if (n_rows == 0) return ALS_OK;
   ALS_REQUIRE(row_ptr && col && val && X_out && status_dev, ALS_EINVAL,
               "als_fold_in: null pointer");
-  ALS_REQUIRE(n_src == 0 || Y_src, ALS_EINVAL, "als_fold_in: null Y_src");
-  ALS_REQUIRE((reinterpret_cast<uintptr_t>(Y_src) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(X_out) & 15) == 0,
-              ALS_EINVAL, "als_fold_in: Y_src / X_out not 16-byte aligned");
+  if (int rc = row_check_source("als_fold_in", n_src, Y_src, X_out)) return rc;
   hipStream_t st = as_stream(stream);
   const int nb = als_k_pad(k) / 16;
   const int lds = fi_lds(k, 16 * nb).total_bytes;
-  const unsigned grid = (unsigned)std::min<int64_t>(n_rows, kFiMaxBlocks);
-#define ALS_FI_LAUNCH(NB, IMP)                                                                  \
-  do {                                                                                          \
-    ALS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fold_in_kernel<NB, IMP>),        \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));              \
-    fold_in_kernel<NB, IMP><<<grid, kFiThreads, lds, st>>>(                                     \
-        row_ptr, col, val, n_rows, Y_src, n_src, ld, k, reg, alpha, yty_packed, X_out, ld_out,  \
-        n_used_out, status_dev);                                                                \
-  } while (0)
-#define ALS_FI_MODE(NB)            \
-  do {                             \
-    if (implicit)                  \
-      ALS_FI_LAUNCH(NB, true);     \
-    else                           \
-      ALS_FI_LAUNCH(NB, false);    \
-  } while (0)
-  switch (nb) {
-    case 1: ALS_FI_MODE(1); break;
-    case 2: ALS_FI_MODE(2); break;
-    case 4: ALS_FI_MODE(4); break;
-    default: ALS_FI_MODE(8); break;
-  }
-#undef ALS_FI_MODE
-#undef ALS_FI_LAUNCH
-  ALS_LAUNCH_CHECK();
-  return ALS_OK;
+  const unsigned grid = (unsigned)std::min<int64_t>(n_rows, kRowMaxBlocks);
+  return row_dispatch(nb, implicit, [&](auto nbc, auto imp) -> int {
+    constexpr auto kernel = &fold_in_kernel<decltype(nbc)::value, decltype(imp)::value>;
+    ALS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    kernel<<<grid, kRowThreads, lds, st>>>(row_ptr, col, val, n_rows, Y_src, n_src, ld, k, reg,
+                                           alpha, yty_packed, X_out, ld_out, n_used_out,
+                                           status_dev);
+    ALS_LAUNCH_CHECK();
+    return ALS_OK;
+  });
 }
 
 }  // extern "C"

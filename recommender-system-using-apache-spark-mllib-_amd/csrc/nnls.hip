@@ -13,10 +13,10 @@
 //            task forms the task's Gram exactly as a short row does and writes its fp64
 //            accumulators, b and the two counts to the task's workspace slot.
 //   solve    One 256-thread workgroup per row.  A short row forms its Gram in place (the
-//            arithmetic of K7: 32 ratings staged at a time, thread (a, b) of a 16 x 16 grid
-//            owns the entries (a + 16 p, b + 16 q), q <= p, fp64, rating order); a long row
-//            sums its slots in slot order.  YtY and reg * n go on there, and A is written to
-//            LDS as a full symmetric KP x KP fp64 matrix.
+//            code shared with K7 through row_system.h: 32 ratings staged at a time, thread
+//            (a, b) of a 16 x 16 grid owns the entries (a + 16 p, b + 16 q), q <= p, fp64,
+//            rating order); a long row sums its slots in slot order.  YtY and reg * n go on
+//            there, and A is written to LDS as a full symmetric KP x KP fp64 matrix.
 //   nnls     G = 256 / KP threads share a row of A; thread i * G owns element i of x, dir,
 //            lastDir, grad, res and b in registers, and x and the direction are published
 //            in LDS for the matrix-vector products.  Every scalar that decides control flow
@@ -28,35 +28,30 @@
 // The result is deterministic: nothing depends on which workgroup runs when.
 #include <algorithm>
 
-#include "als_common.h"
+#include "row_system.h"
 
 namespace als {
-
-constexpr int kNnMaxRank = 128;
-constexpr int kNnThreads = 256;
-constexpr int kNnBatch = 32;         // ratings gathered per step (K7's)
-constexpr int kNnMaxBlocks = 65536;  // blocks stride over the rows / tasks past this
 
 // Dynamic LDS of one block.  A (KP rows of LDA doubles) comes first; the gather buffer of the
 // Gram stage aliases its head (32 * KP floats <= KP * 32 doubles <= A).
 template <int NB>
 struct NnShape {
   static constexpr int KP = 16 * NB;
-  static constexpr int G = kNnThreads / KP;  // threads per row of A
+  static constexpr int G = kRowThreads / KP;  // threads per row of A
   static constexpr int LDA = KP + G;         // 32 lanes of a ds_read_b64 hit 32 different banks
   static constexpr int JT = KP / G;          // columns per thread
   static constexpr int NACC = NB * (NB + 1) / 2;
   static constexpr int A_DOUBLES = KP * LDA;
   // A | x | dir | wa | wb | 4 reduction sites of [4 waves][4] | col | counts, flags
-  static constexpr int DOUBLES = A_DOUBLES + 2 * KP + 2 * kNnBatch + 4 * 16;
-  static constexpr int BYTES = DOUBLES * 8 + kNnBatch * 4 + 8 * 4;
+  static constexpr int DOUBLES = A_DOUBLES + 2 * KP + 2 * kRowBatch + 4 * 16;
+  static constexpr int BYTES = DOUBLES * 8 + kRowBatch * 4 + 8 * 4;
   // one task's workspace slot: the accumulators and b in thread layout, then n and n+
-  static constexpr int64_t SLOT_DOUBLES = (int64_t)(NACC + 1) * kNnThreads + 2;
+  static constexpr int64_t SLOT_DOUBLES = (int64_t)(NACC + 1) * kRowThreads + 2;
 };
 
 static inline int64_t nn_slot_doubles(int kp) {
   const int nb = kp / 16;
-  return (int64_t)(nb * (nb + 1) / 2 + 1) * kNnThreads + 2;
+  return (int64_t)(nb * (nb + 1) / 2 + 1) * kRowThreads + 2;
 }
 
 struct NnSmem {
@@ -80,95 +75,11 @@ __device__ __forceinline__ NnSmem nn_smem(void* base) {
   m.sx = m.A + S::A_DOUBLES;
   m.sd = m.sx + S::KP;
   m.swa = m.sd + S::KP;
-  m.swb = m.swa + kNnBatch;
-  m.sred = m.swb + kNnBatch;
+  m.swb = m.swa + kRowBatch;
+  m.sred = m.swb + kRowBatch;
   m.scol = reinterpret_cast<int*>(m.sred + 4 * 16);
-  m.scnt = m.scol + kNnBatch;
+  m.scnt = m.scol + kRowBatch;
   return m;
-}
-
-// The Gram of the ratings [pb, pe) in the caller's accumulators (K7's gather / gram steps,
-// the same arithmetic in the same order).  n_used / n_pos are valid in wave 0.  Ends on a
-// barrier: ybuf is free when it returns.
-template <int NB, bool IMPLICIT>
-__device__ __forceinline__ void nn_gram(const NnSmem& m, int64_t pb, int64_t pe,
-                                        const int32_t* __restrict__ col,
-                                        const float* __restrict__ val,
-                                        const float* __restrict__ Y, int64_t n_src, int ld, int k,
-                                        float alpha, double (&acc)[NnShape<NB>::NACC],
-                                        double& bacc, int& n_used, int& n_pos) {
-  constexpr int KP = 16 * NB;
-  constexpr int P4 = KP / 4;
-  constexpr int PIECES = kNnBatch * P4;
-  const int t = threadIdx.x;
-  const int ta = t >> 4, tb = t & 15;
-  const int lane = t & 63;
-  for (int64_t s0 = pb; s0 < pe; s0 += kNnBatch) {
-    if (t < 64) {  // wave 0: the batch's ids and weights
-      bool used = false, pos = false;
-      if (lane < kNnBatch) {
-        const int64_t s = s0 + lane;
-        int c = -1;
-        double wa = 0.0, wb = 0.0;
-        if (s < pe) {
-          c = col[s];
-          const double r = (double)val[s];
-          used = c >= 0 && (int64_t)c < n_src;
-          if (used) {
-            pos = r > 0.0;
-            if (IMPLICIT) {
-              const double c1 = (double)alpha * fabs(r);
-              wa = c1;
-              wb = pos ? 1.0 + c1 : 0.0;
-            } else {
-              wa = 1.0;
-              wb = r;
-            }
-          } else {
-            c = -1;
-          }
-        }
-        m.scol[lane] = c;
-        m.swa[lane] = wa;
-        m.swb[lane] = wb;
-      }
-      n_used += __popcll(__ballot(used));
-      n_pos += __popcll(__ballot(pos));
-    }
-    __syncthreads();
-    for (int g = t; g < PIECES; g += kNnThreads) {  // the batch's factor rows
-      const int e = g / P4, c0 = (g % P4) * 4;
-      const int c = m.scol[e];
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (c >= 0 && c0 < k) {  // c0 < k <= ld and ld % 4 == 0: the piece lies inside the row
-        v = *reinterpret_cast<const float4*>(Y + (int64_t)c * ld + c0);
-        if (c0 + 1 >= k) v.y = 0.f;
-        if (c0 + 2 >= k) v.z = 0.f;
-        if (c0 + 3 >= k) v.w = 0.f;
-      }
-      *reinterpret_cast<float4*>(m.ybuf + e * KP + c0) = v;
-    }
-    __syncthreads();
-    const int nb = pe - s0 < kNnBatch ? (int)(pe - s0) : kNnBatch;
-    for (int e = 0; e < nb; ++e) {
-      const float* ye = m.ybuf + e * KP;
-      const double wa = m.swa[e];
-      double yj[NB], wyi[NB];
-#pragma unroll
-      for (int p = 0; p < NB; ++p) {
-        wyi[p] = wa * (double)ye[ta + 16 * p];
-        yj[p] = (double)ye[tb + 16 * p];
-      }
-#pragma unroll
-      for (int p = 0; p < NB; ++p) {
-#pragma unroll
-        for (int q = 0; q <= p; ++q)
-          acc[p * (p + 1) / 2 + q] = fma(wyi[p], yj[q], acc[p * (p + 1) / 2 + q]);
-      }
-      if (t < KP) bacc = fma(m.swb[e], (double)ye[t], bacc);
-    }
-    __syncthreads();  // the next batch (or A) overwrites ybuf
-  }
 }
 
 // ---- schedule: sort keys, task counts ----
@@ -194,7 +105,7 @@ __global__ __launch_bounds__(256) void nnls_keys_kernel(const int64_t* __restric
 
 // ---- partial: one task of a long row -> its slot ----
 template <int NB, bool IMPLICIT>
-__global__ __launch_bounds__(kNnThreads) void nnls_partial_kernel(
+__global__ __launch_bounds__(kRowThreads) void nnls_partial_kernel(
     const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
     const float* __restrict__ val, int64_t n_rows, const float* __restrict__ Y, int64_t n_src,
     int ld, int k, float alpha, int64_t chunk, const int32_t* __restrict__ slot_begin,
@@ -223,14 +134,15 @@ __global__ __launch_bounds__(kNnThreads) void nnls_partial_kernel(
     for (int i = 0; i < S::NACC; ++i) acc[i] = 0.0;
     double bacc = 0.0;
     int n_used = 0, n_pos = 0;
-    nn_gram<NB, IMPLICIT>(m, pb, pe, col, val, Y, n_src, ld, k, alpha, acc, bacc, n_used, n_pos);
+    row_gram<NB, IMPLICIT>(pb, pe, col, val, Y, n_src, ld, k, alpha, m.scol, m.swa, m.swb, m.ybuf,
+                           acc, bacc, n_used, n_pos);
     double* const sl = slots + task * S::SLOT_DOUBLES;
 #pragma unroll
-    for (int i = 0; i < S::NACC; ++i) sl[i * kNnThreads + t] = acc[i];
-    sl[S::NACC * kNnThreads + t] = bacc;
+    for (int i = 0; i < S::NACC; ++i) sl[i * kRowThreads + t] = acc[i];
+    sl[S::NACC * kRowThreads + t] = bacc;
     if (t == 0) {
-      sl[(S::NACC + 1) * kNnThreads] = (double)n_used;
-      sl[(S::NACC + 1) * kNnThreads + 1] = (double)n_pos;
+      sl[(S::NACC + 1) * kRowThreads] = (double)n_used;
+      sl[(S::NACC + 1) * kRowThreads + 1] = (double)n_pos;
     }
   }
 }
@@ -290,7 +202,7 @@ __device__ __forceinline__ bool nn_stop(double step, double ndir, double nx) {
 
 // ---- solve: one row per workgroup ----
 template <int NB, bool IMPLICIT>
-__global__ __launch_bounds__(kNnThreads) void nnls_solve_kernel(
+__global__ __launch_bounds__(kRowThreads) void nnls_solve_kernel(
     const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
     const float* __restrict__ val, int64_t n_rows, const int32_t* __restrict__ order,
     const float* __restrict__ Y, int64_t n_src, int ld, int k, float reg, float alpha,
@@ -327,16 +239,16 @@ __global__ __launch_bounds__(kNnThreads) void nnls_solve_kernel(
       for (int64_t s = sb; s < se; ++s) {
         const double* const sl = slots + s * S::SLOT_DOUBLES;
 #pragma unroll
-        for (int i = 0; i < S::NACC; ++i) acc[i] += sl[i * kNnThreads + t];
-        bacc += sl[S::NACC * kNnThreads + t];
-        cn += sl[(S::NACC + 1) * kNnThreads];
-        cp += sl[(S::NACC + 1) * kNnThreads + 1];
+        for (int i = 0; i < S::NACC; ++i) acc[i] += sl[i * kRowThreads + t];
+        bacc += sl[S::NACC * kRowThreads + t];
+        cn += sl[(S::NACC + 1) * kRowThreads];
+        cp += sl[(S::NACC + 1) * kRowThreads + 1];
       }
       n_used = (int)cn;
       n_pos = (int)cp;
     } else {
-      nn_gram<NB, IMPLICIT>(m, pb, pe, col, val, Y, n_src, ld, k, alpha, acc, bacc, n_used,
-                            n_pos);
+      row_gram<NB, IMPLICIT>(pb, pe, col, val, Y, n_src, ld, k, alpha, m.scol, m.swa, m.swb,
+                             m.ybuf, acc, bacc, n_used, n_pos);
     }
     if (t == 0) {
       m.scnt[0] = n_used;
@@ -349,7 +261,7 @@ __global__ __launch_bounds__(kNnThreads) void nnls_solve_kernel(
     float* const xr = X + row * (int64_t)ld_out;
     if (n_used_out && t == 0) n_used_out[row] = n_all;
     if (n_all == 0) {  // no used entry: b = 0, the solver's answer at its first test
-      for (int c = t; c < ld_out; c += kNnThreads) xr[c] = 0.f;
+      for (int c = t; c < ld_out; c += kRowThreads) xr[c] = 0.f;
       if (iters_out && t == 0) iters_out[row] = 0;
       __syncthreads();  // scnt and sd are rewritten by the next row
       continue;
@@ -430,7 +342,7 @@ __global__ __launch_bounds__(kNnThreads) void nnls_solve_kernel(
       last_norm = ngrad;
     }
     if (own) xr[ri] = (float)x;
-    for (int c = k + t; c < ld_out; c += kNnThreads) xr[c] = 0.f;
+    for (int c = k + t; c < ld_out; c += kRowThreads) xr[c] = 0.f;
     if (iters_out && t == 0) iters_out[row] = iterno;
     __syncthreads();  // A, sx, sd, scnt and the reduction sites are rewritten by the next row
   }
@@ -516,7 +428,7 @@ using namespace als;
 extern "C" {
 
 size_t als_nnls_workspace_bytes(int64_t n_rows, int64_t nnz, int32_t k, int32_t chunk) {
-  if (n_rows <= 0 || nnz < 0 || k < 1 || k > kNnMaxRank || chunk < 1) return 0;
+  if (n_rows <= 0 || nnz < 0 || k < 1 || k > kRowMaxRank || chunk < 1) return 0;
   NnArenaSize a;
   nn_layout(a, n_rows, als_k_pad(k), nn_max_slots(n_rows, nnz, chunk), nullptr);
   return a.off + 256;
@@ -527,25 +439,15 @@ int als_nnls_rows(const int64_t* row_ptr, const int32_t* col, const float* val, 
                   int implicit, float alpha, const double* yty_packed, int32_t chunk,
                   float* X_out, int32_t ld_out, int32_t* n_used_out, int32_t* iters_out, void* ws,
                   size_t ws_bytes, void* stream) {
-  ALS_REQUIRE(k >= 1 && k <= kNnMaxRank, ALS_EUNSUPPORTED,
-              "als_nnls_rows: rank %d not in [1, %d]", k, kNnMaxRank);
-  ALS_REQUIRE(ld >= k && ld % 4 == 0, ALS_EINVAL,
-              "als_nnls_rows: ld %d must be >= k and a multiple of 4", ld);
+  if (int rc = row_check_args("als_nnls_rows", k, ld, n_rows, n_src, reg, alpha, implicit,
+                              yty_packed))
+    return rc;
   ALS_REQUIRE(ld_out >= k && ld_out % 4 == 0, ALS_EINVAL,
               "als_nnls_rows: ld_out %d must be >= k and a multiple of 4", ld_out);
-  ALS_REQUIRE(n_rows >= 0 && n_rows < (int64_t(1) << 31) - 1, ALS_EINVAL,
-              "als_nnls_rows: n_rows outside [0, 2^31 - 1)");
-  ALS_REQUIRE(n_src >= 0 && n_src < (int64_t(1) << 31), ALS_EINVAL,
-              "als_nnls_rows: n_src outside [0, 2^31)");
   ALS_REQUIRE(chunk >= 1, ALS_EINVAL, "als_nnls_rows: chunk %d must be >= 1", chunk);
-  ALS_REQUIRE(reg >= 0.f && alpha >= 0.f, ALS_EINVAL, "als_nnls_rows: reg/alpha must be >= 0");
-  ALS_REQUIRE(!implicit || yty_packed, ALS_EINVAL, "als_nnls_rows: implicit needs yty_packed");
   if (n_rows == 0) return ALS_OK;
   ALS_REQUIRE(row_ptr && col && val && X_out, ALS_EINVAL, "als_nnls_rows: null pointer");
-  ALS_REQUIRE(n_src == 0 || Y_src, ALS_EINVAL, "als_nnls_rows: null Y_src");
-  ALS_REQUIRE((reinterpret_cast<uintptr_t>(Y_src) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(X_out) & 15) == 0,
-              ALS_EINVAL, "als_nnls_rows: Y_src / X_out not 16-byte aligned");
+  if (int rc = row_check_source("als_nnls_rows", n_src, Y_src, X_out)) return rc;
   ALS_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, ALS_EINVAL,
               "als_nnls_rows: workspace null or not 16-byte aligned");
   const int kp = als_k_pad(k);
@@ -577,43 +479,29 @@ int als_nnls_rows(const int64_t* row_ptr, const int32_t* col, const float* val, 
     slot_begin = W.slot_begin;
   }
 
-  const int nb = kp / 16;
-  const unsigned grid = (unsigned)std::min<int64_t>(n_rows, kNnMaxBlocks);
-  const unsigned pgrid = (unsigned)std::min<int64_t>(W.max_slots, kNnMaxBlocks);
-#define ALS_NN_LAUNCH(NB, IMP)                                                                   \
-  do {                                                                                           \
-    const int lds = NnShape<NB>::BYTES;                                                          \
-    if (pgrid > 0) {                                                                             \
-      ALS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&nnls_partial_kernel<NB, IMP>),  \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds));             \
-      nnls_partial_kernel<NB, IMP><<<pgrid, kNnThreads, lds, st>>>(                              \
-          row_ptr, col, val, n_rows, Y_src, n_src, ld, k, alpha, (int64_t)chunk, slot_begin,     \
-          W.max_slots, W.slots);                                                                 \
-      ALS_LAUNCH_CHECK();                                                                        \
-    }                                                                                            \
-    ALS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&nnls_solve_kernel<NB, IMP>),      \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));               \
-    nnls_solve_kernel<NB, IMP><<<grid, kNnThreads, lds, st>>>(                                   \
-        row_ptr, col, val, n_rows, order, Y_src, n_src, ld, k, reg, alpha, yty_packed,           \
-        slot_begin, W.max_slots, W.slots, X_out, ld_out, n_used_out, iters_out);                 \
-  } while (0)
-#define ALS_NN_MODE(NB)            \
-  do {                             \
-    if (implicit)                  \
-      ALS_NN_LAUNCH(NB, true);     \
-    else                           \
-      ALS_NN_LAUNCH(NB, false);    \
-  } while (0)
-  switch (nb) {
-    case 1: ALS_NN_MODE(1); break;
-    case 2: ALS_NN_MODE(2); break;
-    case 4: ALS_NN_MODE(4); break;
-    default: ALS_NN_MODE(8); break;
-  }
-#undef ALS_NN_MODE
-#undef ALS_NN_LAUNCH
-  ALS_LAUNCH_CHECK();
-  return ALS_OK;
+  const unsigned grid = (unsigned)std::min<int64_t>(n_rows, kRowMaxBlocks);
+  const unsigned pgrid = (unsigned)std::min<int64_t>(W.max_slots, kRowMaxBlocks);
+  return row_dispatch(kp / 16, implicit, [&](auto nbc, auto imp) -> int {
+    constexpr int NB = decltype(nbc)::value;
+    constexpr auto partial = &nnls_partial_kernel<NB, decltype(imp)::value>;
+    constexpr auto solve = &nnls_solve_kernel<NB, decltype(imp)::value>;
+    const int lds = NnShape<NB>::BYTES;
+    if (pgrid > 0) {
+      ALS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(partial),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+      partial<<<pgrid, kRowThreads, lds, st>>>(row_ptr, col, val, n_rows, Y_src, n_src, ld, k,
+                                               alpha, (int64_t)chunk, slot_begin, W.max_slots,
+                                               W.slots);
+      ALS_LAUNCH_CHECK();
+    }
+    ALS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(solve),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    solve<<<grid, kRowThreads, lds, st>>>(row_ptr, col, val, n_rows, order, Y_src, n_src, ld, k,
+                                          reg, alpha, yty_packed, slot_begin, W.max_slots, W.slots,
+                                          X_out, ld_out, n_used_out, iters_out);
+    ALS_LAUNCH_CHECK();
+    return ALS_OK;
+  });
 }
 
 }  // extern "C"
