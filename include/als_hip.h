@@ -607,6 +607,47 @@ int als_nnls_rows(const int64_t* row_ptr, const int32_t* col, const float* val, 
                   int32_t chunk, float* X_out, int32_t ld_out, int32_t* n_used_out,
                   int32_t* iters_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- K14: diversified lists (maximal marginal relevance, Carbonell & Goldstein 1998;
+ *      intra-list similarity, Ziegler et al. 2005) ------------------------------------- */
+
+/* Added under ABI 9 without a version bump: two new symbols only, nothing existing changes.
+ * als_diversify: re-ranks each query row's candidate pool.  Per row a pool of m slots
+ * (1 <= m <= 256), idx int32 [n_q, m] and score f32 [n_q, m] as als_topk / als_topk_filtered
+ * return them (dense rows of V, open slots -1 / -inf), against the other side's table
+ * V [n_v, ld] of rank k; columns [k, ld) are ignored whatever they hold.
+ *   live slot: 0 <= idx < n_v and a finite score; every other slot is dead and never
+ *     picked.  Duplicate indices in a pool are separate candidates.
+ *   rel_j = (s_j - s_min) / (s_max - s_min) in fp64 over the row's live slots, 1 for all
+ *     when s_max == s_min.
+ *   unit vector = v_j / |v_j|, the norm in fp64 over columns [0, k), stored in fp32; a row
+ *     with zero norm or a non-finite entry has the zero vector, so its cosine with
+ *     everything is 0 (it can still be picked).  cos(j, s) = <unit_j, unit_s>, summed in
+ *     fp32 in ascending column order.
+ *   greedy: step 0 picks the live slot with the largest rel; step t >= 1 the live unpicked
+ *     slot with the largest lam * rel_j - (1 - lam) * max_{u < t} cos(j, s_u), in fp64 over
+ *     the fp32 cosines; ties go to the lowest slot position at every step; it stops after
+ *     `top` picks or when the live slots run out.
+ * out_idx int32 [n_q, top] / out_score f32 [n_q, top]: the picked slots' idx and their
+ * original scores bit for bit, in pick order (no longer score-descending); open slots
+ * -1 / -inf.  out_ils f64 [n_q]: the mean of cos over the unordered pairs of the picked
+ * list, NaN with fewer than two picks.  At lam = 1 the output is the live prefix of a
+ * score-descending pool exactly.  lam is a float, as reg and alpha are everywhere in this
+ * ABI, and is widened to fp64 in the kernel.  Two calls give bit-identical output.
+ * als_list_similarity: out f64 [n_q] = the same mean over the slots of idx int32 [n_q, m]
+ * with 0 <= idx < n_v (m <= 256), NaN with fewer than two: the intra-list similarity of
+ * lists that came from anywhere.
+ * 1 <= k <= 128 and 1 <= m <= 256 (ALS_EUNSUPPORTED outside); ld >= k and a multiple of 4,
+ * V 16-byte aligned, 1 <= top <= m, lam in [0, 1] (a NaN is outside), n_v < 2^31,
+ * 0 <= n_q < 2^31 - 1 and non-null pointers (ALS_EINVAL otherwise), all checked on the host
+ * before any launch; n_q == 0 is a no-op.  No workspace. */
+int als_diversify(const float* V, int64_t n_v, int32_t ld, int32_t k,
+                  const int32_t* idx, const float* score, int64_t n_q, int32_t m,
+                  int32_t top, float lam,
+                  int32_t* out_idx, float* out_score, double* out_ils, void* stream);
+int als_list_similarity(const float* V, int64_t n_v, int32_t ld, int32_t k,
+                        const int32_t* idx, int64_t n_q, int32_t m,
+                        double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

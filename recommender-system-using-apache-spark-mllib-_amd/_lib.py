@@ -100,6 +100,8 @@ SIGNATURES = {
     "als_nnls_workspace_bytes": (SZ, [I64, I64, I32, I32]),
     "als_nnls_rows": (ctypes.c_int, [P, P, P, I64, P, I64, I32, I32, F32, ctypes.c_int, F32, P,
                                      I32, P, I32, P, P, P, SZ, P]),
+    "als_diversify": (ctypes.c_int, [P, I64, I32, I32, P, P, I64, I32, I32, F32, P, P, P, P]),
+    "als_list_similarity": (ctypes.c_int, [P, I64, I32, I32, P, I64, I32, P, P]),
 }
 
 ABI_VERSION = 9

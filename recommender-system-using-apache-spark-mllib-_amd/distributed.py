@@ -44,7 +44,8 @@ import torch
 import torch.distributed as dist
 
 from .engine import id_offset
-from .filters import (reject_sharded_explain, reject_sharded_filters, reject_sharded_fold_in,
+from .filters import (reject_sharded_diversify, reject_sharded_explain, reject_sharded_filters,
+                      reject_sharded_fold_in,
                       reject_sharded_full_rank, reject_sharded_nonnegative,
                       reject_sharded_objective, reject_sharded_regression,
                       reject_sharded_similar)
@@ -972,6 +973,16 @@ class ShardedALS:
     def similar_all(self, top: int, user_side: bool = False, *, candidates=None):
         """ALSCore.similar_all is not offered on the sharded engine yet."""
         reject_sharded_similar()
+
+    def recommend_diverse(self, top: int, user_side: bool = True, *, ids=None,
+                          trade_off: float = 0.7, pool=None, exclude=None, candidates=None,
+                          chunk_rows=None):
+        """ALSCore.recommend_diverse is not offered on the sharded engine yet."""
+        reject_sharded_diversify(sharded_engine=True)
+
+    def list_similarity(self, id_lists, user_side: bool = True):
+        """ALSCore.list_similarity is not offered on the sharded engine yet."""
+        reject_sharded_diversify(sharded_engine=True)
 
     def regression_metrics(self, users, items, ratings, through_origin: bool = False) -> dict:
         """ALSCore.regression_metrics is not offered on the sharded engine yet."""

@@ -735,6 +735,71 @@ def similar_rows_unit(rows: Optional[torch.Tensor], T: torch.Tensor, n: int, ran
     return idx, sc
 
 
+DIVERSIFY_MAX_POOL = 256  # als_diversify / als_list_similarity: slots per row
+# Pool arrays (idx int32 + score f32 per slot) ALSCore.recommend_diverse keeps alive at once.
+DIVERSIFY_POOL_BYTES = 1 << 30
+
+
+def _check_lists(idx: torch.Tensor, n_v: int, rank: int) -> None:
+    if idx.dim() != 2:
+        raise ValueError(f"idx must be [n_q, m], got shape {tuple(idx.shape)}")
+    if not 1 <= int(idx.shape[1]) <= DIVERSIFY_MAX_POOL:
+        raise ValueError(f"lists must have 1 to {DIVERSIFY_MAX_POOL} slots, got {idx.shape[1]}")
+    if not 1 <= int(rank) <= MAX_RANK:
+        raise ValueError(f"rank must be in [1, {MAX_RANK}], got {rank}")
+    if int(n_v) < 0:
+        raise ValueError("n_v must be >= 0")
+
+
+def diversify_rows(idx: torch.Tensor, sc: torch.Tensor, V: torch.Tensor, n_v: int, rank: int,
+                   top: int, lam: float):
+    """K14 (als_diversify): maximal-marginal-relevance re-ranking of each row's candidate
+    pool.  idx int32 [n_q, m] / sc f32 [n_q, m]: the pool as topk_rows / topk_rows_filtered
+    return it (dense rows of V [n_v, ld], open slots -1 / -inf), m <= DIVERSIFY_MAX_POOL;
+    1 <= top <= m; lam in [0, 1] (1 = pure relevance, 0 = pure diversity after the first
+    pick; rounded to fp32 on its way to the library).  Returns (idx int32 [n_q, top], score
+    f32 [n_q, top], ils f64 [n_q]): the picks in pick order with their original scores, open
+    slots -1 / -inf, and each list's mean pairwise cosine (NaN under two picks).  The
+    contract is in include/als_hip.h."""
+    _check_lists(idx, n_v, rank)
+    if tuple(sc.shape) != tuple(idx.shape):
+        raise ValueError(f"idx {tuple(idx.shape)} and sc {tuple(sc.shape)} must have one shape")
+    n_q, m = int(idx.shape[0]), int(idx.shape[1])
+    top, lam = int(top), float(lam)
+    if not 1 <= top <= m:
+        raise ValueError(f"top must be in [1, pool = {m}], got {top}")
+    if not 0.0 <= lam <= 1.0:   # (a NaN fails both comparisons)
+        raise ValueError(f"lam must be in [0, 1], got {lam}")
+    L = _lib.lib()
+    dev = V.device
+    idx = idx.to(torch.int32).contiguous()
+    sc = sc.to(torch.float32).contiguous()
+    out_i = torch.empty((n_q, top), dtype=torch.int32, device=dev)
+    out_s = torch.empty((n_q, top), dtype=torch.float32, device=dev)
+    ils = torch.empty(n_q, dtype=torch.float64, device=dev)
+    check(L.als_diversify(ptr(V), int(n_v), V.shape[1], int(rank), ptr(idx), ptr(sc), n_q, m, top,
+                          lam, ptr(out_i), ptr(out_s), ptr(ils), stream_ptr(dev)),
+          "als_diversify")
+    return out_i, out_s, ils
+
+
+def list_similarity_rows(idx: torch.Tensor, V: torch.Tensor, n_v: int, rank: int):
+    """K14 (als_list_similarity): ils f64 [n_q], the mean cosine over the unordered pairs of
+    the slots of idx int32 [n_q, m] (m <= DIVERSIFY_MAX_POOL) that name a row of V [n_v, ld]
+    (0 <= idx < n_v; anything else, such as the -1 of an open slot, is skipped); NaN with
+    fewer than two.  A row of V without a direction (zero norm, NaN, Inf) counts with
+    cosine 0."""
+    _check_lists(idx, n_v, rank)
+    L = _lib.lib()
+    dev = V.device
+    idx = idx.to(torch.int32).contiguous()
+    n_q, m = int(idx.shape[0]), int(idx.shape[1])
+    out = torch.empty(n_q, dtype=torch.float64, device=dev)
+    check(L.als_list_similarity(ptr(V), int(n_v), V.shape[1], int(rank), ptr(idx), n_q, m,
+                                ptr(out), stream_ptr(dev)), "als_list_similarity")
+    return out
+
+
 MAX_RANK_AT = 256  # als_rank_metrics: list positions scored per row
 
 
@@ -1356,6 +1421,88 @@ class ALSCore:
                 torch.empty((qi.n, 0), dtype=torch.float32, device=self.device)
         idx, sc = similar_rows_unit(None, T, qi.n, self.rank, t, bits)
         return qi.ids(), ids_of(qi.ids(), idx), sc
+
+    # ---- K14: lists that cover more than one taste ----
+    def recommend_diverse(self, top: int, user_side: bool = True, *, ids=None,
+                          trade_off: float = 0.7, pool=None, exclude=None, candidates=None,
+                          chunk_rows=None):
+        """recommend_all / recommend_subset re-ranked for diversity: K5 (or filtered K5) lists
+        `pool` candidates per row, then K14 (als_diversify) picks `top` of them greedily by
+        maximal marginal relevance, trade_off * relevance - (1 - trade_off) * (largest cosine
+        to what the list already holds); trade_off = 1 gives the plain lists.
+        ids: None = every row of the side in dense order, else the distinct known ids
+        ascending (as recommend_subset).  pool: None = min(256, max(4 top, 50)), at most
+        DIVERSIFY_MAX_POOL, capped at the other side's row count.  exclude / candidates as
+        recommend_all.  Returns (keys [n], ids [n, t], scores [n, t], ils f64 [n]) on the
+        device, t = min(top, pool): the picks in pick order with their K5 scores (not
+        descending), open slots score -inf, and each list's intra-list similarity (mean
+        pairwise cosine, NaN under two picks).
+        The query rows go through in chunks of chunk_rows (None: as many as keep the pool
+        arrays within DIVERSIFY_POOL_BYTES); the result does not depend on the chunking."""
+        if self.U is None or self.V is None:
+            raise ValueError("recommend_diverse needs factors: fit() the core or build it "
+                             "from_factors")
+        top, lam = int(top), float(trade_off)
+        if top < 1:
+            raise ValueError(f"top must be >= 1, got {top}")
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError(f"trade_off must be in [0, 1], got {trade_off}")
+        if pool is None:
+            pool = min(DIVERSIFY_MAX_POOL, max(4 * top, 50))
+        pool = int(pool)
+        if not 1 <= pool <= DIVERSIFY_MAX_POOL:
+            raise ValueError(f"pool must be in [1, {DIVERSIFY_MAX_POOL}], got {pool}")
+        if chunk_rows is not None and int(chunk_rows) < 1:
+            raise ValueError(f"chunk_rows must be >= 1, got {chunk_rows}")
+        qi, Q, oi, Vo = self._sides(user_side)
+        pool = min(pool, oi.n)
+        t = min(top, pool)
+        dev = self.device
+        if ids is None:
+            keys, rows, n = qi.ids(), None, qi.n
+        else:
+            keys = torch.unique(_to_device(ids, torch.int32, dev))
+            rows = qi.rows_of(keys)
+            keys, rows = keys[rows >= 0], rows[rows >= 0]
+            n = int(keys.numel())
+        out_i = torch.empty((n, t), dtype=torch.int32, device=dev)
+        out_s = torch.empty((n, t), dtype=torch.float32, device=dev)
+        ils = torch.empty(n, dtype=torch.float64, device=dev)
+        if n == 0 or t == 0:
+            return keys, out_i, out_s, ils
+        filtered = exclude is not None or candidates is not None
+        beg, end, col, bits = self._filter_args(exclude, candidates, user_side, rows)
+        step = int(chunk_rows) if chunk_rows is not None else max(1, DIVERSIFY_POOL_BYTES
+                                                                 // (8 * pool))
+        for r0 in range(0, n, step):
+            r1 = min(n, r0 + step)
+            Qc = Q[r0:r1] if rows is None else Q.index_select(0, rows[r0:r1]).contiguous()
+            if filtered:
+                pi, ps = topk_rows_filtered(
+                    Qc, r1 - r0, Vo, oi.n, self.rank, pool,
+                    None if beg is None else beg[r0:r1].contiguous(),
+                    None if end is None else end[r0:r1].contiguous(), col, bits)
+            else:
+                pi, ps = topk_rows(Qc, r1 - r0, Vo, oi.n, self.rank, pool)
+            out_i[r0:r1], out_s[r0:r1], ils[r0:r1] = diversify_rows(pi, ps, Vo, oi.n, self.rank,
+                                                                    t, lam)
+            del pi, ps
+        return keys, ids_of(oi.ids(), out_i), out_s, ils
+
+    def list_similarity(self, id_lists, user_side: bool = True):
+        """Intra-list similarity of any lists: id_lists [n, m] (m <= DIVERSIFY_MAX_POOL) hold
+        ids of the OTHER side — items for user_side=True, as recommend_all's ids — and the
+        result is f64 [n] on the device, each list's mean pairwise cosine between the factor
+        rows of its known ids (an unknown id is an open slot; NaN under two known ids)."""
+        if self.U is None or self.V is None:
+            raise ValueError("list_similarity needs factors: fit() the core or build it "
+                             "from_factors")
+        _, _, oi, Vo = self._sides(user_side)
+        lists = _to_device(id_lists, torch.int32, self.device)
+        if lists.dim() != 2:
+            raise ValueError(f"id_lists must be [n, m], got shape {tuple(lists.shape)}")
+        rows = oi.rows_of(lists).to(torch.int32)
+        return list_similarity_rows(rows, Vo, oi.n, self.rank)
 
     # ---- K7: rows the model has never seen ----
     def _fold_in(self, ids, other_ids, ratings, reg, implicit, alpha, user_side,

@@ -20,7 +20,7 @@ import torch
 __all__ = ["pack_allow_bits", "exclusion_lists", "relevance_lists", "ragged_rows",
            "relevance_lists_weighted", "reject_sharded_filters", "reject_sharded_fold_in",
            "reject_sharded_regression", "reject_sharded_full_rank", "reject_sharded_explain",
-           "reject_sharded_similar", "reject_sharded_nonnegative"]
+           "reject_sharded_similar", "reject_sharded_nonnegative", "reject_sharded_diversify"]
 
 
 def pack_allow_bits(rows: torch.Tensor, n_v: int) -> torch.Tensor:
@@ -151,6 +151,21 @@ def reject_sharded_nonnegative() -> None:
     raise NotImplementedError(
         "nonnegative=True (the NNLS solver, K13) is not supported by the sharded engine "
         "(ShardedALS) yet: fit nonnegative factors on a single-GPU ALSCore")
+
+
+def reject_sharded_diversify(sharded_engine: bool = False) -> None:
+    """Raises when this process is one rank of a torch.distributed world of more than one
+    process: what such a rank holds is the sharded engine, which carries recommend_diverse /
+    list_similarity with the single-GPU signature and refuses them (sharded_engine=True: the
+    call comes from that engine itself), as it refuses similar."""
+    if not sharded_engine:
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+            return
+    raise NotImplementedError(
+        "recommend_diverse / list_similarity are not supported by the sharded engine "
+        "(ShardedALS) yet: diversify lists on a single-GPU ALSCore (e.g. ALSCore.from_factors "
+        "over the gathered factors)")
 
 
 def reject_sharded_regression() -> None:

@@ -602,3 +602,88 @@ class ALSModel:
         ids = check_integers(columns_of(dataset, (col,))[0], col)
         return self._recs_df(col, *self._core.recommend_subset(
             ids, int(numUsers), False, **self._filters(exclude, candidates, False)))
+
+    # -- diversified lists (K14): maximal marginal relevance over a K5 candidate pool --
+    def _diverse_df(self, key_col, keys, ids, sc, ils):
+        df = self._recs_df(key_col, keys, ids, sc)
+        df["intraListSimilarity"] = ils.cpu().numpy()
+        return df
+
+    def _diverse(self, num, tradeOff, user_side: bool, ids, pool, exclude, candidates):
+        return self._core.recommend_diverse(
+            int(num), user_side, ids=ids, trade_off=float(tradeOff), pool=pool,
+            **self._filters(exclude, candidates, user_side))
+
+    def recommendForAllUsersDiverseArrays(self, numItems: int, tradeOff: float = 0.7, *,
+                                          pool=None, exclude=None, candidates=None):
+        """Device tensors (user ids [n_u], item ids [n_u, t], scores [n_u, t], intra-list
+        similarity f64 [n_u]); see recommendForAllUsersDiverse."""
+        return self._diverse(numItems, tradeOff, True, None, pool, exclude, candidates)
+
+    def recommendForAllUsersDiverse(self, numItems: int, tradeOff: float = 0.7, *, pool=None,
+                                    exclude=None, candidates=None):
+        """recommendForAllUsers re-ranked so that a list covers more than one taste:
+        DataFrame[userCol, recommendations: list of (item, rating), intraListSimilarity].
+        The `pool` best items of each user (None: min(256, max(4 numItems, 50))) are the
+        candidates; numItems of them are picked one by one, each the candidate with the
+        largest tradeOff * relevance - (1 - tradeOff) * (largest cosine to the items already
+        picked) — maximal marginal relevance, relevance = the rating rescaled to [0, 1] over
+        the pool.  tradeOff = 1 is recommendForAllUsers; lower values trade rating for
+        variety.  The list is in pick order with the plain ratings, so it is not descending.
+        intraListSimilarity: the mean cosine between the factors of the listed items (NaN
+        under two items) — compare with intraListSimilarity(recommendForAllUsers(...)).
+        exclude / candidates as recommendForAllUsers.  Works on a loaded model; only
+        exclude="train" needs the ratings."""
+        return self._diverse_df(self._p["userCol"], *self.recommendForAllUsersDiverseArrays(
+            numItems, tradeOff, pool=pool, exclude=exclude, candidates=candidates))
+
+    def recommendForAllItemsDiverse(self, numUsers: int, tradeOff: float = 0.7, *, pool=None,
+                                    exclude=None, candidates=None):
+        """recommendForAllUsersDiverse from the item side: DataFrame[itemCol,
+        recommendations: list of (user, rating), intraListSimilarity]."""
+        return self._diverse_df(self._p["itemCol"], *self._diverse(
+            numUsers, tradeOff, False, None, pool, exclude, candidates))
+
+    def recommendForUserSubsetDiverse(self, dataset, numItems: int, tradeOff: float = 0.7, *,
+                                      pool=None, exclude=None, candidates=None):
+        """recommendForAllUsersDiverse for the distinct known users of `dataset[userCol]`."""
+        col = self._p["userCol"]
+        ids = check_integers(columns_of(dataset, (col,))[0], col)
+        return self._diverse_df(col, *self._diverse(numItems, tradeOff, True, ids, pool, exclude,
+                                                    candidates))
+
+    def recommendForItemSubsetDiverse(self, dataset, numUsers: int, tradeOff: float = 0.7, *,
+                                      pool=None, exclude=None, candidates=None):
+        col = self._p["itemCol"]
+        ids = check_integers(columns_of(dataset, (col,))[0], col)
+        return self._diverse_df(col, *self._diverse(numUsers, tradeOff, False, ids, pool, exclude,
+                                                    candidates))
+
+    def intraListSimilarity(self, recommendations):
+        """Intra-list similarity of lists in the shape recommendForAllUsers /
+        recommendForAllItems return (a key column and `recommendations`: lists of (id,
+        rating) of at most 256 entries): DataFrame[key column, intraListSimilarity], the mean
+        cosine between the factors of each list's ids (ids the model does not know are
+        skipped; NaN under two known ids).  The key column says which side the lists hold:
+        userCol = lists of items, itemCol = lists of users."""
+        import pandas as pd
+        p = self._p
+        user_side = p["userCol"] in recommendations
+        key_col = p["userCol"] if user_side else p["itemCol"]
+        if key_col not in recommendations:
+            raise ValueError(f"recommendations must have a {p['userCol']!r} or {p['itemCol']!r} "
+                             "column")
+        lists = [[int(a) for a, _ in recs] for recs in recommendations["recommendations"]]
+        m = max([len(x) for x in lists] + [1])
+        _, _, oi, Vo = self._core._sides(user_side)
+        ids = np.zeros((len(lists), m), np.int64)
+        known = np.zeros((len(lists), m), bool)
+        for r, x in enumerate(lists):
+            ids[r, :len(x)] = x
+            known[r, :len(x)] = True
+        dev = self._core.device
+        rows = oi.rows_of(torch.as_tensor(ids, device=dev))
+        rows = torch.where(torch.as_tensor(known, device=dev), rows, -1).to(torch.int32)
+        ils = _engine.list_similarity_rows(rows, Vo, oi.n, self._core.rank)
+        return pd.DataFrame({key_col: np.asarray(recommendations[key_col]),
+                             "intraListSimilarity": ils.cpu().numpy()})

@@ -217,6 +217,36 @@ class MatrixFactorizationModel:
                           if np.isfinite(s)])
                 for k, ri, rs in zip(keys, ids, sc)]
 
+    def recommendProductsDiverse(self, user: int, num: int, tradeOff: float = 0.7, *, pool=None,
+                                 exclude=None, candidates=None):
+        """recommendProducts re-ranked by maximal marginal relevance (K14): (list of Rating in
+        pick order, intra-list similarity of the list).  The `pool` best products (None:
+        min(256, max(4 num, 50))) are the candidates; each pick maximises tradeOff *
+        relevance - (1 - tradeOff) * (largest cosine to the products already picked), so
+        tradeOff = 1 is recommendProducts and lower values trade rating for variety.
+        KeyError for an unknown user."""
+        user = int(user)
+        keys, ids, sc, ils = self._core.recommend_diverse(
+            int(num), True, ids=[user], trade_off=float(tradeOff), pool=pool,
+            **self._filters(exclude, candidates, True))
+        if keys.numel() == 0:
+            raise KeyError(f"unknown id {user}")
+        ids, sc = ids.cpu().numpy()[0], sc.cpu().numpy()[0]
+        return ([Rating(user, int(a), float(s)) for a, s in zip(ids, sc) if np.isfinite(s)],
+                float(ils[0]))
+
+    def recommendProductsForUsersDiverse(self, num: int, tradeOff: float = 0.7, *, pool=None,
+                                         exclude=None, candidates=None):
+        """recommendProductsDiverse for every user: [(user, list of Rating, intra-list
+        similarity)]."""
+        keys, ids, sc, ils = self._core.recommend_diverse(
+            int(num), True, trade_off=float(tradeOff), pool=pool,
+            **self._filters(exclude, candidates, True))
+        keys, ids, sc, ils = (x.cpu().numpy() for x in (keys, ids, sc, ils))
+        return [(int(k), [Rating(int(k), int(a), float(s)) for a, s in zip(ri, rs)
+                          if np.isfinite(s)], float(v))
+                for k, ri, rs, v in zip(keys, ids, sc, ils)]
+
     def foldInUsers(self, ratings, lambda_: float, *, implicit: bool = False,
                     alpha: float = 0.01, nonnegative: bool = False):
         """Factors for users that are not in the model, from their (user, product,

@@ -43,8 +43,8 @@ def _engine_of(model):
 
 
 def personal_recommendations_fold_in(model, rated: Iterable[Sequence], movies: Iterable[Sequence],
-                                     counts, reg: float, min_count: int = 75, num: int = 20
-                                     ) -> List[Tuple[float, str, int]]:
+                                     counts, reg: float, min_count: int = 75, num: int = 20,
+                                     trade_off=None) -> List[Tuple[float, str, int]]:
     """personal_recommendations' output — (predicted rating, movie name, number of
     ratings), highest prediction first — for a user who is NOT in the model, without the
     retrain of R:218: the user's factor row is folded in from `rated` against the fixed
@@ -54,7 +54,11 @@ def personal_recommendations_fold_in(model, rated: Iterable[Sequence], movies: I
 
     rated:  the new user's (user, movie, rating) triples (one user id throughout)
     reg:    the lambda the model was trained with (explicit feedback, as the reference)
-    movies / counts: as personal_recommendations."""
+    movies / counts: as personal_recommendations.
+    trade_off: None = the list above.  A number in [0, 1]: the filtered list is taken
+        min(256, max(4 num, 50)) deep and re-ranked by maximal marginal relevance (K14,
+        engine.diversify_rows) down to `num`, in pick order: 1 keeps the order above, lower
+        values trade predicted rating for variety among the movies' factors."""
     rated = [(int(u), int(m), float(r)) for u, m, r, *_ in rated]
     if len({u for u, _, _ in rated}) > 1:
         raise ValueError("rated must hold the ratings of one user")
@@ -70,11 +74,20 @@ def personal_recommendations_fold_in(model, rated: Iterable[Sequence], movies: I
     if not rated or not cand:
         return []
     u, m, r = (np.asarray(x) for x in zip(*rated))
-    _, ids, sc = _engine_of(model).recommend_new(
-        u.astype(np.int32), m.astype(np.int32), r.astype(np.float32), int(num), reg=float(reg),
+    eng = _engine_of(model)
+    depth = int(num) if trade_off is None else min(256, max(4 * int(num), 50))
+    _, ids, sc = eng.recommend_new(
+        u.astype(np.int32), m.astype(np.int32), r.astype(np.float32), depth, reg=float(reg),
         exclude_rated=True, candidates=np.asarray(cand, np.int32))
     if ids.shape[0] == 0:   # none of the rated movies is known to the model
         return []
+    if trade_off is not None and ids.shape[1] > 0:
+        from . import engine as _engine
+        rows = eng.iidx.rows_of(ids).to(ids.dtype)
+        rows[~sc.isfinite()] = -1   # (an open slot carries a placeholder id)
+        idx, sc, _ = _engine.diversify_rows(rows, sc, eng.V, eng.n_items, eng.rank,
+                                            min(int(num), int(ids.shape[1])), float(trade_off))
+        ids = _engine.ids_of(eng.iidx.ids(), idx)
     ids, sc = ids.cpu().numpy()[0], sc.cpu().numpy()[0]
     return [(float(s), titles[int(a)], count_of(int(a))) for a, s in zip(ids, sc)
             if np.isfinite(s)]
