@@ -24,8 +24,10 @@
 //       four table rows go into each instruction, A and B operands from the same registers, no
 //       LDS.  Columns >= k and rows past the end enter as 0.
 //   fold kernels            per-block partials are summed in ascending block order (each
-//       thread a strided ascending subsequence, then a fixed tree for the scalar sums).
+//       thread a strided ascending subsequence, then a fixed tree for the scalar sums:
+//       partial_sums.h).
 #include "als_common.h"
+#include "partial_sums.h"
 
 namespace als {
 
@@ -158,32 +160,6 @@ __global__ __launch_bounds__(256) void objective_side_kernel(
     double a = sm[threadIdx.x * 16];
     for (int q = 1; q < 16; ++q) a += sm[threadIdx.x * 16 + q];
     partial[(int64_t)kObjOut * blockIdx.x + threadIdx.x] = a;
-  }
-}
-
-// Tree sum of the 256 threads' values (thread t with t + s, s = 128 .. 1), returned to thread 0.
-__device__ __forceinline__ double block_tree_sum(double mine, double* sm) {
-  const int t = threadIdx.x;
-  __syncthreads();  // sm may still be read from the previous field
-  sm[t] = mine;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if (t < s) sm[t] += sm[t + s];
-    __syncthreads();
-  }
-  return sm[0];
-}
-
-// One block: field f of out = the per-block partials of field f, each thread its blocks in
-// ascending order, then the tree.
-__global__ __launch_bounds__(256) void objective_final_kernel(const double* __restrict__ partial,
-                                                              int64_t nb, double* __restrict__ out) {
-  __shared__ double sm[256];
-  for (int f = 0; f < kObjOut; ++f) {
-    double a = 0.0;
-    for (int64_t b = threadIdx.x; b < nb; b += 256) a += partial[kObjOut * b + f];
-    a = block_tree_sum(a, sm);
-    if (threadIdx.x == 0) out[f] = a;
   }
 }
 
@@ -371,7 +347,7 @@ int als_objective_side(const int64_t* row_ptr, const int32_t* col, const float* 
                                                       ld, k, implicit != 0, (double)alpha,
                                                       partial);
   ALS_LAUNCH_CHECK();
-  objective_final_kernel<<<1, 256, 0, st>>>(partial, nb, out);
+  sum_partials_kernel<kObjOut><<<1, 256, 0, st>>>(partial, nb, out);
   ALS_LAUNCH_CHECK();
   return ALS_OK;
 }

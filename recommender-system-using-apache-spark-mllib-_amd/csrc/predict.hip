@@ -10,9 +10,10 @@
 // in fp64 and the group reduces with xor-shuffles.  Unknown ids (outside the
 // map or mapped to -1) give NaN (predict) or are skipped (RMSE), which is the
 // inner-join semantics of predictAll + computeError.  The RMSE partials are
-// per-block fp64 sums reduced in a fixed order, so the result is bitwise
-// reproducible run to run.
+// per-block fp64 sums reduced in a fixed order (partial_sums.h), so the result
+// is bitwise reproducible run to run.
 #include "als_common.h"
+#include "partial_sums.h"
 
 namespace als {
 
@@ -72,31 +73,6 @@ __global__ __launch_bounds__(256) void rmse_partial_kernel(
   }
 }
 
-// Single-block fixed-order reduction of the per-block partials.
-__global__ __launch_bounds__(256) void rmse_final_kernel(const double* __restrict__ partial,
-                                                         int64_t nb, double* __restrict__ out) {
-  __shared__ double ssum[256], scnt[256];
-  double a = 0.0, c = 0.0;
-  for (int64_t b = threadIdx.x; b < nb; b += 256) {
-    a += partial[2 * b];
-    c += partial[2 * b + 1];
-  }
-  ssum[threadIdx.x] = a;
-  scnt[threadIdx.x] = c;
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      ssum[threadIdx.x] += ssum[threadIdx.x + s];
-      scnt[threadIdx.x] += scnt[threadIdx.x + s];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    out[0] = ssum[0];
-    out[1] = scnt[0];
-  }
-}
-
 }  // namespace als
 
 using namespace als;
@@ -142,7 +118,7 @@ int als_rmse_partial(const int32_t* u, const int32_t* i, const float* r, int64_t
   rmse_partial_kernel<<<(unsigned)nb, 256, 0, st>>>(u, i, r, n, umap, umap_size, imap, imap_size,
                                                     U, V, ld, k, partial);
   ALS_LAUNCH_CHECK();
-  rmse_final_kernel<<<1, 256, 0, st>>>(partial, nb, sse_count_out);
+  sum_partials_kernel<2><<<1, 256, 0, st>>>(partial, nb, sse_count_out);
   ALS_LAUNCH_CHECK();
   return ALS_OK;
 }

@@ -15,9 +15,10 @@
 // (a table made once per call by a one-block launch), so a row whose first
 // min(m, at) positions are all hits scores NDCG 1.0 exactly.  All arithmetic is fp64.
 // Row values are added up per wave in row order, the four waves of a block in wave
-// order, and the per-block partials by a single block in a fixed order: the sums are
-// bitwise reproducible run to run.
+// order, and the per-block partials by a single block in a fixed order (partial_sums.h):
+// the sums are bitwise reproducible run to run.
 #include "als_common.h"
+#include "partial_sums.h"
 
 namespace als {
 
@@ -129,30 +130,6 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(
   }
 }
 
-// Single-block fixed-order reduction of the per-block partials.
-__global__ __launch_bounds__(256) void rank_final_kernel(const double* __restrict__ partial,
-                                                         int64_t nb, double* __restrict__ out) {
-  __shared__ double ssum[kRmSums][256];
-  double a[kRmSums];
-#pragma unroll
-  for (int i = 0; i < kRmSums; ++i) a[i] = 0.0;
-  for (int64_t b = threadIdx.x; b < nb; b += 256) {
-#pragma unroll
-    for (int i = 0; i < kRmSums; ++i) a[i] += partial[kRmSums * b + i];
-  }
-#pragma unroll
-  for (int i = 0; i < kRmSums; ++i) ssum[i][threadIdx.x] = a[i];
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-#pragma unroll
-      for (int i = 0; i < kRmSums; ++i) ssum[i][threadIdx.x] += ssum[i][threadIdx.x + s];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x < kRmSums) out[threadIdx.x] = ssum[threadIdx.x][0];
-}
-
 }  // namespace als
 
 using namespace als;
@@ -193,7 +170,7 @@ int als_rank_metrics(const int32_t* idx, int64_t n_q, int32_t idx_ld, int32_t at
   rank_metrics_kernel<<<(unsigned)nb, 256, 0, st>>>(idx, n_q, idx_ld, at, rel_begin, rel_end,
                                                     rel_col, tab, per_row_out, partial);
   ALS_LAUNCH_CHECK();
-  rank_final_kernel<<<1, 256, 0, st>>>(partial, nb, sums_out);
+  sum_partials_kernel<kRmSums><<<1, 256, 0, st>>>(partial, nb, sums_out);
   ALS_LAUNCH_CHECK();
   return ALS_OK;
 }

@@ -44,6 +44,8 @@
 // from the first sweep.  All counts are integers, so the result does not depend on the
 // order of the LDS atomics.
 #include "als_common.h"
+#include "partial_sums.h"
+#include "rank_key.h"
 
 namespace als {
 
@@ -64,19 +66,6 @@ static inline int64_t fr_blocks(int64_t n_q) {
   return g < 1 ? 1 : (g > kFrMaxBlocks ? kFrMaxBlocks : g);
 }
 
-struct RpFilt {
-  const int64_t* ex_begin;
-  const int64_t* ex_end;
-  const int32_t* ex_col;
-  const uint32_t* allow;
-};
-
-// Monotone key of a score that is not NaN: unsigned order = score order, -0 and +0 equal.
-__device__ __forceinline__ uint32_t rp_key(float s) {
-  const uint32_t u = __float_as_uint(s + 0.f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // The one score chain of K9 (see the header): ascending d, one fmaf per term.
 __device__ __forceinline__ float rp_dot(const float* __restrict__ q, const float* __restrict__ v,
                                         int k) {
@@ -92,23 +81,6 @@ __device__ __forceinline__ float rp_dot(const float* __restrict__ q, const float
   }
   for (; d < k; ++d) s = __builtin_fmaf(q[d], v[d], s);
   return s;
-}
-
-__device__ __forceinline__ bool rp_allowed(const RpFilt& f, int j) {
-  return !f.allow || ((f.allow[j >> 5] >> (j & 31)) & 1u);
-}
-
-// j in ex_col[ex_begin[row] .. ex_end[row])  (ascending, duplicates allowed)
-__device__ __forceinline__ bool rp_excluded(const RpFilt& f, int64_t row, int j) {
-  if (!f.ex_begin) return false;
-  const int64_t end = f.ex_end[row];
-  int64_t lo = f.ex_begin[row], hi = end;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (f.ex_col[mid] < j) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo < end && f.ex_col[lo] == j;
 }
 
 __device__ __forceinline__ uint32_t rp_table_key(const uint64_t* __restrict__ keys, int slot) {
@@ -134,7 +106,7 @@ __device__ __forceinline__ void rp_place(const uint64_t* __restrict__ keys, int*
 __global__ __launch_bounds__(kRpThreads) void rank_positions_kernel(
     const float* __restrict__ Q, int64_t n_q, const float* __restrict__ V, int n_v, int ld, int k,
     const int64_t* __restrict__ rel_begin, const int64_t* __restrict__ rel_end,
-    const int32_t* __restrict__ rel_col, RpFilt f, int32_t* __restrict__ above,
+    const int32_t* __restrict__ rel_col, RowFilter f, int32_t* __restrict__ above,
     int32_t* __restrict__ tied, int32_t* __restrict__ n_adm) {
   extern __shared__ float4 rp_smem[];  // Qs [kp][kRpRows], then Vs [kRpDepth][kRpVStride]
   __shared__ uint64_t keys[kRpTable];  // (row << 44) | (score key << 12) | slot
@@ -209,9 +181,9 @@ __global__ __launch_bounds__(kRpThreads) void rank_positions_kernel(
         const int64_t e = sBeg[row] + (slot - sSeg[row]);
         const int c = rel_col[e];
         uint32_t key = kRpBadKey;
-        if (c >= 0 && c < n_v && rp_allowed(f, c) && !rp_excluded(f, row0 + row, c)) {
+        if (c >= 0 && c < n_v && row_allowed(f, c) && !row_excluded(f, row0 + row, c)) {
           const float s = rp_dot(Q + (row0 + row) * ld, V + (int64_t)c * ld, k);
-          if (s == s) key = rp_key(s);
+          if (s == s) key = score_key(s);
         }
         if (key == kRpBadKey) {
           above[e] = -1;
@@ -267,7 +239,7 @@ __global__ __launch_bounds__(kRpThreads) void rank_positions_kernel(
           const int v = v0 + vr;
           const float nan = __builtin_nanf("");
           float4 x = make_float4(nan, nan, nan, nan);
-          if (v < n_v && rp_allowed(f, v)) {
+          if (v < n_v && row_allowed(f, v)) {
             x = make_float4(0.f, 0.f, 0.f, 0.f);
             if (d < kp) {
               x = *reinterpret_cast<const float4*>(V + (int64_t)v * ld + d);
@@ -303,7 +275,7 @@ __global__ __launch_bounds__(kRpThreads) void rank_positions_kernel(
           const float s = acc[i][j];
           if (s == s) {
             ++nloc[i];
-            const uint32_t key = rp_key(s);
+            const uint32_t key = score_key(s);
             if (key >= lowkey[i]) rp_place(keys, cnt, seg[i], nv[i], key, 1);
           }
         }
@@ -327,11 +299,11 @@ __global__ __launch_bounds__(kRpThreads) void rank_positions_kernel(
           const int c = f.ex_col[e];
           if (c < 0 || c >= n_v) continue;
           if (e > beg && f.ex_col[e - 1] == c) continue;  // a duplicate: counted once
-          if (!rp_allowed(f, c)) continue;                // the sweep never counted it
+          if (!row_allowed(f, c)) continue;                // the sweep never counted it
           const float s = rp_dot(Q + (row0 + row) * ld, V + (int64_t)c * ld, k);
           if (!(s == s)) continue;
           ++gone;
-          if (rnv > 0) rp_place(keys, cnt, rseg, rnv, rp_key(s), -1);
+          if (rnv > 0) rp_place(keys, cnt, rseg, rnv, score_key(s), -1);
         }
         if (pass == 0 && gone) atomicAdd(&sAdm[row], -gone);
       }
@@ -456,31 +428,6 @@ __global__ __launch_bounds__(256) void full_rank_metrics_kernel(
   }
 }
 
-// Single-block fixed-order reduction of the per-block partials.
-__global__ __launch_bounds__(256) void full_rank_final_kernel(const double* __restrict__ partial,
-                                                              int64_t nb,
-                                                              double* __restrict__ out) {
-  __shared__ double ssum[kFrSums][256];
-  double a[kFrSums];
-#pragma unroll
-  for (int i = 0; i < kFrSums; ++i) a[i] = 0.0;
-  for (int64_t b = threadIdx.x; b < nb; b += 256) {
-#pragma unroll
-    for (int i = 0; i < kFrSums; ++i) a[i] += partial[kFrSums * b + i];
-  }
-#pragma unroll
-  for (int i = 0; i < kFrSums; ++i) ssum[i][threadIdx.x] = a[i];
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-#pragma unroll
-      for (int i = 0; i < kFrSums; ++i) ssum[i][threadIdx.x] += ssum[i][threadIdx.x + s];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x < kFrSums) out[threadIdx.x] = ssum[threadIdx.x][0];
-}
-
 }  // namespace als
 
 using namespace als;
@@ -510,9 +457,8 @@ int als_rank_positions(const float* Q, int64_t n_q, const float* V, int64_t n_v,
               "als_rank_positions: n_v outside [0, 2^31 - 1)");
   ALS_REQUIRE(n_q < (int64_t)kRpRows * 0x7fffffffLL, ALS_EINVAL,
               "als_rank_positions: n_q too large");
-  const bool any_ex = ex_begin || ex_end || ex_col;
-  ALS_REQUIRE(!any_ex || (ex_begin && ex_end && ex_col), ALS_EINVAL,
-              "als_rank_positions: ex_begin, ex_end and ex_col must be all null or all set");
+  const int rc = check_exclusion_args("als_rank_positions", ex_begin, ex_end, ex_col);
+  if (rc != ALS_OK) return rc;
   if (n_q == 0) return ALS_OK;
   ALS_REQUIRE(Q && rel_begin && rel_end && rel_col && above_out && tied_out && n_adm_out,
               ALS_EINVAL, "als_rank_positions: null pointer");
@@ -525,7 +471,7 @@ int als_rank_positions(const float* Q, int64_t n_q, const float* V, int64_t n_v,
   const int lds = (int)sizeof(float) * (kp * kRpRows + kRpDepth * kRpVStride);
   ALS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rank_positions_kernel),
                               hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  const RpFilt f{ex_begin, ex_end, ex_col, allow_bits};
+  const RowFilter f{ex_begin, ex_end, ex_col, allow_bits};
   const unsigned nb = (unsigned)((n_q + kRpRows - 1) / kRpRows);
   rank_positions_kernel<<<nb, kRpThreads, (size_t)lds, st>>>(
       Q, n_q, V, (int)n_v, ld, k, rel_begin, rel_end, rel_col, f, above_out, tied_out, n_adm_out);
@@ -555,7 +501,7 @@ int als_full_rank_metrics(const int32_t* above, const int32_t* tied, const int32
   full_rank_metrics_kernel<<<(unsigned)nb, 256, 0, st>>>(above, tied, n_adm, n_q, rel_begin,
                                                          rel_end, w, per_row_out, partial);
   ALS_LAUNCH_CHECK();
-  full_rank_final_kernel<<<1, 256, 0, st>>>(partial, nb, sums_out);
+  sum_partials_kernel<kFrSums><<<1, 256, 0, st>>>(partial, nb, sums_out);
   ALS_LAUNCH_CHECK();
   return ALS_OK;
 }

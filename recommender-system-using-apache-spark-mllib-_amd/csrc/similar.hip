@@ -22,7 +22,7 @@
 // (query, row) pair's score is the same bits wherever it is computed.
 //   score = dot * (1 / sqrt(|t|^2)) * inv|q|        (fp32; inv|q| from an fp64 norm)
 // Lists.  Per query a log of `cap` 64-bit keys in LDS (the (monotone score bits | ~index)
-// key of topk.hip, compared exactly).  A key above the query's threshold is appended —
+// key of rank_key.h, compared exactly).  A key above the query's threshold is appended —
 // positions from ballots, no atomics — and a log that the next tile could overflow is cut to
 // its `top` largest keys (sim_compact: bitwise search for the top-th key, then a stable
 // partition), whose smallest becomes the threshold.  The threshold never exceeds the
@@ -38,6 +38,7 @@
 // route that hands the copy to K5; the same launch clears the allow bit of every row that
 // cannot be a neighbour (zero norm, NaN, Inf).
 #include "als_common.h"
+#include "rank_key.h"
 
 #include <algorithm>
 
@@ -52,18 +53,6 @@ constexpr int kSimTileRows = 16;   // table rows per tile: the most keys one til
 constexpr int kSimMergeCap = 512;  // keys of the merge kernel's log
 constexpr int kSimMaxSlices = 4096;
 constexpr int kSimMergeFan = 32;   // slice lists per first-stage merge group
-
-// topk.hip's key: unsigned order = score descending, then index ascending.
-__device__ __forceinline__ uint64_t sim_key(float sc, int id) {
-  const uint32_t u = __float_as_uint(sc + 0.f);  // -0 -> +0
-  const uint32_t o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((uint64_t)o << 32) | (uint32_t)(~id);
-}
-__device__ __forceinline__ float sim_key_score(uint64_t key) {
-  const uint32_t o = (uint32_t)(key >> 32);
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-__device__ __forceinline__ int sim_key_index(uint64_t key) { return (int)~(uint32_t)key; }
 
 // Cut log L (n keys, top < n <= 64 J, unique, all > 0; one wavefront, L in LDS) to its `top`
 // largest keys, in place at the front; returns the smallest kept key.  The top-th largest
@@ -294,7 +283,7 @@ __global__ __launch_bounds__(64) void sim_sweep_kernel(
 #pragma unroll
       for (int v = 0; v < VPL; ++v) {
         const float sc = val[v] * invt * iq[v];
-        const uint64_t key = sim_key(sc, (int)row);
+        const uint64_t key = rank_key(sc, (int)row);
         bool pass = rowok && sc == sc && key > th[v];
         if (pass) {  // admissibility only for a key that would be listed
           if ((int)row == sf[v]) pass = false;
@@ -365,8 +354,8 @@ __global__ __launch_bounds__(64) void sim_merge_kernel(const uint64_t* __restric
       const uint64_t key = L[e];
       int rank = 0;  // keys are unique: the rank is the number of larger keys
       for (int i = 0; i < cnt; ++i) rank += L[i] > key;
-      idx_out[(int64_t)j * top + rank] = sim_key_index(key);
-      score_out[(int64_t)j * top + rank] = sim_key_score(key);
+      idx_out[(int64_t)j * top + rank] = rank_key_index(key);
+      score_out[(int64_t)j * top + rank] = rank_key_score(key);
     } else {
       idx_out[(int64_t)j * top + e] = -1;
       score_out[(int64_t)j * top + e] = -__builtin_inff();

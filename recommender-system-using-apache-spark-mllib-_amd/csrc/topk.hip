@@ -31,6 +31,7 @@
 // powers of two) and unscaled on output.  An all-zero query row scores 0
 // against every V row; its list is the first `top` rows by index.
 #include "als_common.h"
+#include "rank_key.h"
 
 #include <algorithm>
 
@@ -91,61 +92,21 @@ __global__ __launch_bounds__(256) void tk_absmax_kernel(const float* __restrict_
 constexpr int kTopkMax = 256;
 constexpr int kLdsBytes = 160 * 1024;  // per CU on gfx950 (one workgroup may use it all)
 
-// Lists hold (score, index) as one 64-bit key whose unsigned order is the
-// ranking order: high word = the score's bits made monotone (sign flip), low word =
-// ~index (a lower index ranks higher on equal scores).  NaN scores are never keys.
-__device__ __forceinline__ uint64_t tk_key(float sc, int id) {
-  const uint32_t u = __float_as_uint(sc + 0.f);  // -0 -> +0: equal scores, equal bits
-  const uint32_t o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((uint64_t)o << 32) | (uint32_t)(~id);
-}
-__device__ __forceinline__ float tk_key_score(uint64_t key) {
-  const uint32_t o = (uint32_t)(key >> 32);
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-__device__ __forceinline__ int tk_key_index(uint64_t key) { return (int)~(uint32_t)key; }
-constexpr uint64_t kTkKeyOpen = 0;              // unfilled entry: any candidate ranks above it
-constexpr uint64_t kTkKeySentinel = ~0ull;      // entries past `top`: nothing ranks above it
-
 __device__ __forceinline__ bool beats(float s1, int i1, float s2, int i2) {
   return s1 > s2 || (s1 == s2 && i1 < i2);
-}
-
-// Filtered top-k (als_topk_filtered): V row j may be listed by query row r only if bit j
-// of `allow` is set (null: every row) and j is not in ex_col[ex_begin[r] .. ex_end[r])
-// (ascending, duplicates allowed; null: no exclusions).  The arrays are indexed by the
-// launch's query rows (the host offsets ex_begin / ex_end with Q for a sliced launch).
-struct TkFilt {
-  const int64_t* ex_begin;
-  const int64_t* ex_end;
-  const int32_t* ex_col;
-  const uint32_t* allow;
-};
-
-__device__ __forceinline__ bool tk_admit(const TkFilt& f, int64_t row, int j) {
-  if (f.allow && !((f.allow[j >> 5] >> (j & 31)) & 1u)) return false;
-  if (!f.ex_begin) return true;
-  const int64_t end = f.ex_end[row];
-  int64_t lo = f.ex_begin[row], hi = end;
-  while (lo < hi) {  // lower bound of j in the row's range (one exit: no return inside)
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (f.ex_col[mid] < j) lo = mid + 1;
-    else hi = mid;
-  }
-  return !(lo < end && f.ex_col[lo] == j);
 }
 
 // An all-zero query row under a filter: every score is 0, so its list is the first `top`
 // admissible V rows by index (the unfiltered rule restricted to them), the rest open.
 // One wave scans 64 V rows per step.
-__device__ __forceinline__ void tk_zero_row_filtered(const TkFilt& f, int64_t row, int64_t n_v,
+__device__ __forceinline__ void tk_zero_row_filtered(const RowFilter& f, int64_t row, int64_t n_v,
                                                      int top, int32_t* __restrict__ idx_out,
                                                      float* __restrict__ score_out) {
   const int lane = threadIdx.x & 63;
   int cnt = 0;
   for (int64_t base = 0; base < n_v && cnt < top; base += 64) {
     const int64_t j = base + lane;
-    const bool ok = j < n_v && tk_admit(f, row, (int)j);
+    const bool ok = j < n_v && row_admits(f, row, (int)j);
     const uint64_t b = __ballot(ok);
     const int pos = cnt + __popcll(b & ((1ull << lane) - 1));
     if (ok && pos < top) {
@@ -163,7 +124,7 @@ __device__ __forceinline__ void tk_zero_row_filtered(const TkFilt& f, int64_t ro
 // The all-zero query rows among a wave's 16 RG rows (row0 + gr g + rho; live[g] bit rho
 // clear and the row present; live is wave-uniform).
 template <int RG>
-__device__ __forceinline__ void tk_zero_rows_filtered(const TkFilt& f, const unsigned (&live)[RG],
+__device__ __forceinline__ void tk_zero_rows_filtered(const RowFilter& f, const unsigned (&live)[RG],
                                                       int64_t row0, int gr, int64_t n_q,
                                                       int64_t n_v, int top,
                                                       int32_t* __restrict__ idx_out,
@@ -183,7 +144,7 @@ __device__ __forceinline__ void tk_zero_rows_filtered(const TkFilt& f, const uns
 // still filling) and are inadmissible score NaN from here on.  Dead rows (absent: no
 // exclusion range to read; or all zero) likewise.
 template <int RG, class TH>
-__device__ __forceinline__ void tk_drop_inadmissible(const TkFilt& f, floatx4 (&acc)[RG], int j,
+__device__ __forceinline__ void tk_drop_inadmissible(const RowFilter& f, floatx4 (&acc)[RG], int j,
                                                      const TH& th, bool all,
                                                      const unsigned (&live)[RG], int64_t row0,
                                                      int gr) {
@@ -199,7 +160,7 @@ __device__ __forceinline__ void tk_drop_inadmissible(const TkFilt& f, floatx4 (&
       bool drop = false;
       if (acc[g][r] == acc[g][r] && (all || acc[g][r] >= th[g][r])) {
         const bool lv = (live[g] >> (4 * q + r)) & 1u;
-        drop = !lv || !tk_admit(f, row0 + gr * g + r, j);
+        drop = !lv || !row_admits(f, row0 + gr * g + r, j);
       }
       acc[g][r] = drop ? __builtin_nanf("") : acc[g][r];
     }
@@ -235,7 +196,7 @@ __device__ __forceinline__ void topk_offer(const floatx4& acc, int ibase, int64_
     const float sc =
         __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mys), L));
     const int itm = __builtin_amdgcn_readlane(vidx, L);
-    const uint64_t ck = tk_key(sc, itm);
+    const uint64_t ck = rank_key(sc, itm);
     const int slot = slot0 + 4 * (L >> 4) + rL;  // list row within the workgroup
     uint64_t* lkr = lk + slot * top;
     const int n = len[slot];
@@ -271,8 +232,8 @@ __device__ __forceinline__ void topk_offer(const floatx4& acc, int ibase, int64_
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       if (newn == top) {
         const uint64_t kk = lkr[top - 1];
-        const float ks = tk_key_score(kk);
-        const int ki = tk_key_index(kk);
+        const float ks = rank_key_score(kk);
+        const int ki = rank_key_index(kk);
         if (q == (L >> 4)) {
 #pragma unroll
           for (int r = 0; r < 4; ++r)
@@ -317,8 +278,8 @@ __device__ __forceinline__ void topk_write(const uint64_t* __restrict__ lk,
     const int n = len[slot];
     for (int e = lane; e < top; e += 64) {
       const uint64_t kk = e < n ? lk[slot * top + e] : 0ull;
-      idx_out[row * top + e] = e < n ? tk_key_index(kk) : -1;
-      score_out[row * top + e] = e < n ? tk_key_score(kk) * unscale : -__builtin_inff();
+      idx_out[row * top + e] = e < n ? rank_key_index(kk) : -1;
+      score_out[row * top + e] = e < n ? rank_key_score(kk) * unscale : -__builtin_inff();
     }
   }
 }
@@ -652,7 +613,7 @@ __device__ __forceinline__ uint64_t tk_log_kth(const uint64_t (&kv)[J], int T) {
 // configs[4]'s 262,144-user sample: top-100 390 ms vs 233 ms with one group.)
 __host__ __device__ constexpr int tk_nw(int topr) { return topr > 0 ? 8 : 4; }
 // FILT (topk_split_filt_kernel, als_topk_filtered): a refined pair that would reach its
-// row's list or log is first tested for admissibility (tk_admit: one bit test and a
+// row's list or log is first tested for admissibility (row_admits: one bit test and a
 // binary search in the row's exclusion range) and an inadmissible one has its exact
 // score replaced by NaN, which no list, log or threshold accepts — the same treatment
 // as a V row past n_v.  The thresholds therefore are k-th best scores among admissible
@@ -665,7 +626,7 @@ __host__ __device__ constexpr int tk_nw(int topr) { return topr > 0 ? 8 : 4; }
 // filter statement is discarded, so the unfiltered kernels are untouched by it.
 #ifdef ALS_TOPK_FILTERED_TU
 #define ALS_TOPK_KERNEL topk_split_filt_kernel
-#define ALS_TOPK_FILT_PARAM , TkFilt flt
+#define ALS_TOPK_FILT_PARAM , RowFilter flt
 #else
 #define ALS_TOPK_KERNEL topk_split_kernel
 #define ALS_TOPK_FILT_PARAM
@@ -686,7 +647,7 @@ __global__ __launch_bounds__(64 * tk_nw(TOPR)) void ALS_TOPK_KERNEL(const float*
   constexpr bool FILT = true;
 #else
   constexpr bool FILT = false;
-  constexpr TkFilt flt{};  // (named by the discarded FILT statements only)
+  constexpr RowFilter flt{};  // (named by the discarded FILT statements only)
 #endif
   constexpr int NW = tk_nw(TOPR);  // wavefronts
   constexpr int GR = 16 * NW;          // query rows of a row group
@@ -828,7 +789,7 @@ __global__ __launch_bounds__(64 * tk_nw(TOPR)) void ALS_TOPK_KERNEL(const float*
       base += __popcll(b);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    return tk_key_score(P);
+    return rank_key_score(P);
   };
 
   // Tile staging by LDS-DMA (global_load_lds_dwordx4: no VGPRs, no ds_write): the
@@ -943,7 +904,7 @@ __global__ __launch_bounds__(64 * tk_nw(TOPR)) void ALS_TOPK_KERNEL(const float*
         for (int r = 0; r < 4; ++r) {
           const bool ok = acc[g][r] >= tx[g][r];
           const unsigned grp = (unsigned)(__ballot(ok) >> (16 * q)) & 0xFFFFu;
-          if (ok) rowlog(g, 4 * q + r)[lcnt[g][r] + __popc(grp & below)] = tk_key(acc[g][r], bperm[m]);
+          if (ok) rowlog(g, 4 * q + r)[lcnt[g][r] + __popc(grp & below)] = rank_key(acc[g][r], bperm[m]);
           lcnt[g][r] += __popc(grp);
         }
       return;
@@ -989,10 +950,10 @@ __global__ __launch_bounds__(64 * tk_nw(TOPR)) void ALS_TOPK_KERNEL(const float*
           const int mm = __builtin_ctz(msk);
           msk &= msk - 1;
           const float sc = sg[16 * mm];
-          const uint64_t c = tk_key(sc, bperm[mm]);
+          const uint64_t c = rank_key(sc, bperm[mm]);
           if (sc == sc && c > kv[0][0]) tk_insert<NR>(kv[0], c);
         }
-        thr[lane] = kv[0][0] == kTkKeyOpen ? -__builtin_inff() : tk_key_score(kv[0][0]);
+        thr[lane] = kv[0][0] == kTkKeyOpen ? -__builtin_inff() : rank_key_score(kv[0][0]);
       }
       asm volatile("" ::: "memory");
       refresh();
@@ -1240,8 +1201,8 @@ __global__ __launch_bounds__(64 * tk_nw(TOPR)) void ALS_TOPK_KERNEL(const float*
           const uint64_t key = ks[e];
           int r = 0;
           for (int t = 0; t < T; ++t) r += ks[t] > key ? 1 : 0;
-          idx_out[row * top + r] = tk_key_index(key);
-          score_out[row * top + r] = tk_key_score(key) * unscale;
+          idx_out[row * top + r] = rank_key_index(key);
+          score_out[row * top + r] = rank_key_score(key) * unscale;
         }
         for (int e = T + lane; e < top; e += 64) {
           idx_out[row * top + e] = -1;
@@ -1267,8 +1228,8 @@ __global__ __launch_bounds__(64 * tk_nw(TOPR)) void ALS_TOPK_KERNEL(const float*
               }
             } else {
               const bool real = kv[0][j] != kTkKeyOpen;
-              idx_out[row * top + e] = real ? tk_key_index(kv[0][j]) : -1;
-              score_out[row * top + e] = real ? tk_key_score(kv[0][j]) * unscale : -__builtin_inff();
+              idx_out[row * top + e] = real ? rank_key_index(kv[0][j]) : -1;
+              score_out[row * top + e] = real ? rank_key_score(kv[0][j]) * unscale : -__builtin_inff();
             }
           }
         }
@@ -1370,7 +1331,7 @@ struct TkLaunch {
 #else
 #define ALS_TOPK_FILT_ARG
 #endif
-static int topk_launch_split(const TkLaunch& a, const TkFilt& f) {
+static int topk_launch_split(const TkLaunch& a, const RowFilter& f) {
   const int64_t rows_blk = 16 * (int64_t)a.nw * a.rg;
   const int64_t n_blk = (a.n_q + rows_blk - 1) / rows_blk;
   // key logs: launches of at most kTkLogBlocks blocks (one log slab per block)
@@ -1384,7 +1345,7 @@ static int topk_launch_split(const TkLaunch& a, const TkFilt& f) {
       const int64_t r0 = b0 * rows_blk;                                                         \
       const int64_t nq_c = std::min<int64_t>(a.n_q - r0, blk_per * rows_blk);                   \
       const unsigned grid = (unsigned)((nq_c + rows_blk - 1) / rows_blk);                       \
-      TkFilt fs = f; /* the slice's rows: exclusion ranges offset as Q and the outputs */       \
+      RowFilter fs = f; /* the slice's rows: exclusion ranges offset as Q and the outputs */       \
       if (fs.ex_begin) {                                                                        \
         fs.ex_begin += r0;                                                                      \
         fs.ex_end += r0;                                                                        \
@@ -1432,7 +1393,7 @@ static int topk_launch_split(const TkLaunch& a, const TkFilt& f) {
 }
 
 // The filtered instantiations (topk_filtered.hip).
-int topk_launch_filtered(const TkLaunch& a, const TkFilt& f);
+int topk_launch_filtered(const TkLaunch& a, const RowFilter& f);
 
 }  // namespace als
 
@@ -1440,7 +1401,7 @@ using namespace als;
 
 #ifdef ALS_TOPK_FILTERED_TU
 
-int als::topk_launch_filtered(const TkLaunch& a, const TkFilt& f) {
+int als::topk_launch_filtered(const TkLaunch& a, const RowFilter& f) {
   return topk_launch_split(a, f);
 }
 
@@ -1476,7 +1437,7 @@ size_t als_topk_workspace_bytes(int64_t n_q, int64_t n_v, int32_t k, int32_t top
 // and V's preparation; only the sweep kernel differs.
 static int topk_run(const float* Q, int64_t n_q, const float* V, int64_t n_v, int32_t ld,
                     int32_t k, int32_t top, int32_t* idx_out, float* score_out, void* ws,
-                    size_t ws_bytes, void* stream, const TkFilt* flt) {
+                    size_t ws_bytes, void* stream, const RowFilter* flt) {
   ALS_REQUIRE(k >= 1 && k <= 128, ALS_EUNSUPPORTED, "als_topk: rank %d not in [1, 128]", k);
   ALS_REQUIRE(ld >= k && ld % 4 == 0, ALS_EINVAL, "als_topk: bad ld");
   ALS_REQUIRE(top >= 1 && top <= kTopkMax, ALS_EUNSUPPORTED, "als_topk: top %d not in [1, %d]",
@@ -1535,7 +1496,7 @@ static int topk_run(const float* Q, int64_t n_q, const float* V, int64_t n_v, in
   const TkLaunch a{Q, n_q, vsp4, vsp4 + n_v * (kq / 8), perm, vnorm, n_v, ld, k, top, scal,
                    idx_out, score_out, tlog, topk_split_lds_bytes(kq, rg, top, logs),
                    topk_nw(top, logs, rg), rg, kq, logs, st};
-  return flt ? topk_launch_filtered(a, *flt) : topk_launch_split(a, TkFilt{});
+  return flt ? topk_launch_filtered(a, *flt) : topk_launch_split(a, RowFilter{});
 }
 
 int als_topk(const float* Q, int64_t n_q, const float* V, int64_t n_v, int32_t ld, int32_t k,
@@ -1548,13 +1509,12 @@ int als_topk_filtered(const float* Q, int64_t n_q, const float* V, int64_t n_v, 
                       int32_t k, int32_t top, const int64_t* ex_begin, const int64_t* ex_end,
                       const int32_t* ex_col, const uint32_t* allow_bits, int32_t* idx_out,
                       float* score_out, void* ws, size_t ws_bytes, void* stream) {
-  const int n_ex = (ex_begin != nullptr) + (ex_end != nullptr) + (ex_col != nullptr);
-  ALS_REQUIRE(n_ex == 0 || n_ex == 3, ALS_EINVAL,
-              "als_topk_filtered: ex_begin, ex_end and ex_col must all be null or all be set");
-  const TkFilt flt{ex_begin, ex_end, ex_col, allow_bits};
+  const int rc = check_exclusion_args("als_topk_filtered", ex_begin, ex_end, ex_col);
+  if (rc != ALS_OK) return rc;
+  const RowFilter flt{ex_begin, ex_end, ex_col, allow_bits};
   // no filter at all: the unfiltered kernel
   return topk_run(Q, n_q, V, n_v, ld, k, top, idx_out, score_out, ws, ws_bytes, stream,
-                  (n_ex || allow_bits) ? &flt : nullptr);
+                  (ex_begin || allow_bits) ? &flt : nullptr);
 }
 
 }  // extern "C"

@@ -329,7 +329,7 @@ def edge_model():
 @pytest.mark.parametrize("n", [1, 15, 16, 17, 255, 256, 257, 70001])
 def test_predict_rmse_pair_count_edges(edge_model, n):
     """Pair counts around the 16-pair group and the 256-pair block, and 70,001 pairs (274
-    partial blocks: rmse_final_kernel's strided loop).  The last pairs — the ragged end
+    partial blocks: sum_partials_kernel's strided loop).  The last pairs — the ragged end
     of the last group — are the unknown kinds (-1, INT32_MIN, INT32_MAX, id == map size,
     map entry -1) as far as n has room beside one known pair."""
     m = edge_model

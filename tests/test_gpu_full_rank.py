@@ -120,6 +120,15 @@ def test_exact_counts_over_several_passes_of_a_workgroup():
     _check_exact(rng, 7, 1031, 67, np.full(67, 100))
 
 
+def test_exact_counts_and_sums_over_more_than_256_partial_blocks():
+    """1,029 query rows: 258 blocks of metric partials, the last holding one row, so the
+    strided loop of the final sum (sum_partials_kernel) makes a second pass for threads 0
+    and 1."""
+    rng = np.random.default_rng(79)
+    n_q, n_v = 1029, 65
+    _check_exact(rng, 8, n_v, n_q, rng.integers(0, 10, n_q))
+
+
 def test_exact_counts_for_a_row_larger_than_the_table():
     table = E.rank_positions_table()
     rng = np.random.default_rng(78)

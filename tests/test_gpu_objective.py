@@ -126,11 +126,7 @@ def _span_cases():
     }
 
 
-@pytest.mark.parametrize("rank,implicit,alpha", [(17, False, 1.0), (17, True, 40.0),
-                                                 (128, True, 0.01)])
-def test_span_edges_on_both_sides(rank, implicit, alpha):
-    S, cases = _span_cases()
-    assert S % 16 == 0
+def _check_span_cases(cases, rank, implicit, alpha):
     ws = _ws()
     for name, lens in cases.items():
         rng = np.random.default_rng(len(lens) + sum(lens))
@@ -166,6 +162,25 @@ def test_span_edges_on_both_sides(rank, implicit, alpha):
         # both sides hold the same ratings: the data term agrees
         tol = 1e-12 * got["row side"][1]
         assert abs(got["row side"][0] - got["col side"][0]) <= tol, name
+
+
+@pytest.mark.parametrize("rank,implicit,alpha", [(17, False, 1.0), (17, True, 40.0),
+                                                 (128, True, 0.01)])
+def test_span_edges_on_both_sides(rank, implicit, alpha):
+    S, cases = _span_cases()
+    assert S % 16 == 0
+    _check_span_cases(cases, rank, implicit, alpha)
+
+
+@pytest.mark.parametrize("implicit", [False, True])
+def test_more_than_256_partial_blocks(implicit):
+    """257 S + 1 ratings: 258 blocks of partials, the last holding one rating, so the strided
+    loop of the final sum (sum_partials_kernel) makes a second pass for threads 0 and 1."""
+    S = E.objective_span()
+    lens = [S // 4 + 3] * 1000
+    lens.append(257 * S + 1 - sum(lens))
+    assert lens[-1] > 0 and sum(lens) == 257 * S + 1
+    _check_span_cases({"nnz = 257 S + 1": lens}, 8, implicit, 40.0 if implicit else 1.0)
 
 
 # ------------------------------------------------------------------ Gram kernel alone
