@@ -632,8 +632,23 @@ __device__ __forceinline__ void pre_issue(PreStep<TS::NC>& s, const int* __restr
   for (int j = 0; j < 8; ++j) TS::load_pre(base + (uint64_t)(uint32_t)ids[j] * kp, s.w[j]);
 }
 
+// How the pre path keeps its rhs sums.  ONE = false: one tile per dims-block c, the
+// rating words as the MFMA's column operand (column 0 = hi(r), column 1 = lo(r)):
+// C_c[i][0] + C_c[i][1] = b[i * CN + c].  ONE = true: one tile for all dims-blocks,
+// the rating words as the row operand in rows 2c (hi(r)) and 2c + 1 (lo(r)) of
+// dims-block c's two MFMAs and exact zeros in the other rows: C[2c][i] + C[2c+1][i]
+// = b[i * CN + c].  Every entry receives the same products in the same order as
+// with ONE = false (plus exact zeros), so the sums are bit-identical; NR - 1 fewer
+// accumulator tiles stay live through the Gram loop.
+template <class TS, bool ONE>
+struct RhsTiles {
+  static_assert(!ONE || (TS::NR >= 1 && 2 * TS::NR <= 16), "rows 2c, 2c + 1 of one tile");
+  static constexpr int N = ONE ? 1 : TS::NRA;
+};
+
 // f16 operands of one step: ratings (2p, 2p+1) share a dword, hi halves and lo
-// halves; rhs B operand by lane column (m = 0: hi(r), m = 1: lo(r), else 0).
+// halves; rhs operand by lane index m: hi(r) on m = 0, lo(r) on m = 1, else 0
+// (rsel of the caller; one rhs tile: hi(r) on even m, lo(r) on odd m < 2 NR).
 template <class TS>
 __device__ __forceinline__ void pre_operands(const PreStep<TS::NC>& s, uint32_t rsel,
                                              uint32_t (&hi)[TS::NC][4], uint32_t (&lo)[TS::NC][4],
@@ -667,33 +682,58 @@ __device__ __forceinline__ void pin_operands(uint32_t (&hi)[TS::NC][4], uint32_t
   asm volatile("" ::: "memory");
 }
 
-template <class TS>
+template <class TS, bool ONE = false>
 __device__ __forceinline__ void pre_mfma(const uint32_t (&hi)[TS::NC][4],
                                          const uint32_t (&lo)[TS::NC][4], const uint32_t (&rb)[4],
-                                         floatx4 (&acc)[TS::N], floatx4 (&accb)[TS::NRA]) {
+                                         floatx4 (&acc)[TS::N],
+                                         floatx4 (&accb)[RhsTiles<TS, ONE>::N]) {
   split_mfma<TS>(hi, lo, acc);
-  const half8v b = as_h8(rb);
+  if constexpr (ONE) {
+    const int m = threadIdx.x & 15;
 #pragma unroll
-  for (int c = 0; c < TS::NR; ++c) {
-    accb[c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_h8(hi[c]), b, accb[c], 0, 0, 0);
-    accb[c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_h8(lo[c]), b, accb[c], 0, 0, 0);
+    for (int c = 0; c < TS::NR; ++c) {
+      uint32_t rc[4];  // the rating words in rows 2c, 2c + 1 only
+#pragma unroll
+      for (int p = 0; p < 4; ++p) rc[p] = (m >> 1) == c ? rb[p] : 0u;
+      const half8v a = as_h8(rc);
+      accb[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, as_h8(hi[c]), accb[0], 0, 0, 0);
+      accb[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, as_h8(lo[c]), accb[0], 0, 0, 0);
+    }
+  } else {
+    const half8v b = as_h8(rb);
+#pragma unroll
+    for (int c = 0; c < TS::NR; ++c) {
+      accb[c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_h8(hi[c]), b, accb[c], 0, 0, 0);
+      accb[c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_h8(lo[c]), b, accb[c], 0, 0, 0);
+    }
   }
+}
+
+// Byte selector of this lane's rhs operand words (pre_operands).
+template <class TS, bool ONE>
+__device__ __forceinline__ uint32_t pre_rsel() {
+  const int m = threadIdx.x & 15;
+  if constexpr (ONE)
+    return m >= 2 * TS::NR ? 0x0C0C0C0Cu : ((m & 1) ? 0x07060302u : 0x05040100u);
+  else
+    return m == 0 ? 0x05040100u : (m == 1 ? 0x07060302u : 0x0C0C0C0Cu);
 }
 
 // Gram tiles (acc, x 2^2ey) and rhs tiles (accb, x 2^(ey+er)) of ratings
 // [pb, pe) from the split table.  d0 = this lane's first dim (m * CN); st: 128
 // words of wave-private LDS staging.  Pipeline as gram_accumulate_split; the
 // gathers of the step after the last one read the zero row (never consumed).
-template <class TS>
+template <class TS, bool ONE = false>
 __device__ __forceinline__ void gram_accumulate_pre(
     const int32_t* __restrict__ col, const float* __restrict__ val, int64_t pb, int64_t pe,
     const uint32_t* __restrict__ Ysp, uint32_t kp, int zero_row, float sr, int d0,
-    floatx4 (&acc)[TS::N], floatx4 (&accb)[TS::NRA], int* __restrict__ st, float& rmax) {
-  const int lane = threadIdx.x & 63, m = lane & 15;
+    floatx4 (&acc)[TS::N], floatx4 (&accb)[RhsTiles<TS, ONE>::N], int* __restrict__ st,
+    float& rmax) {
+  const int lane = threadIdx.x & 63;
   int* st_c = st;
   uint32_t* st_r = reinterpret_cast<uint32_t*>(st + 64);
   if (pe <= pb) return;
-  const uint32_t rsel = m == 0 ? 0x05040100u : (m == 1 ? 0x07060302u : 0x0C0C0C0Cu);
+  const uint32_t rsel = pre_rsel<TS, ONE>();
   const uint32_t* base = Ysp + d0;
   auto load_idx = [&](int64_t b, int& ci, float& rv) {
     ci = zero_row;
@@ -728,7 +768,7 @@ __device__ __forceinline__ void gram_accumulate_pre(
       load_idx(pb + 64 * (int64_t)((t >> 1) + 2), ci_n, rv_n);
     }
     pre_issue<TS>(s, st_c, st_r, (t + 1) & 1, base, kp);
-    pre_mfma<TS>(hi, lo, rb, acc, accb);
+    pre_mfma<TS, ONE>(hi, lo, rb, acc, accb);
   }
 }
 
@@ -741,10 +781,10 @@ __device__ __forceinline__ void gram_accumulate_pre2(
     const int32_t* __restrict__ col, const float* __restrict__ val, int64_t pb, int64_t pe,
     const uint32_t* __restrict__ Ysp, uint32_t kp, int zero_row, float sr, int d0,
     floatx4 (&acc)[TS::N], floatx4 (&accb)[TS::NRA], int* __restrict__ st, float& rmax) {
-  const int lane = threadIdx.x & 63, m = lane & 15;
+  const int lane = threadIdx.x & 63;
   // slot b % 2: 64 column indices then 64 split rating words
   if (pe <= pb) return;
-  const uint32_t rsel = m == 0 ? 0x05040100u : (m == 1 ? 0x07060302u : 0x0C0C0C0Cu);
+  const uint32_t rsel = pre_rsel<TS, false>();
   const uint32_t* base = Ysp + d0;
   auto load_idx = [&](int64_t b, int& ci, float& rv) {
     ci = zero_row;
@@ -798,10 +838,20 @@ __device__ __forceinline__ void gram_accumulate_pre2(
 // rhs from the pre path's tiles: b[i*CN + gcol(c)] = C[i][0] + C[i][1] of
 // accb[c], returned in the layout of the split path's partials (lane (0, m)
 // holds dim m*CN + gcol(c), lanes with q > 0 hold 0), times `scale`.
-template <class TS>
-__device__ __forceinline__ void rhs_from_tiles(const floatx4 (&accb)[TS::NRA], float scale,
-                                               float (&bt)[TS::NRA]) {
+// (One rhs tile: rows 2c and 2c + 1, i.e. registers (2c) % 4 and (2c) % 4 + 1 of
+// lane (c / 2, m).)
+template <class TS, bool ONE = false>
+__device__ __forceinline__ void rhs_from_tiles(const floatx4 (&accb)[RhsTiles<TS, ONE>::N],
+                                               float scale, float (&bt)[TS::NRA]) {
   const int lane = threadIdx.x & 63, q = lane >> 4, m = lane & 15;
+  if constexpr (ONE) {
+#pragma unroll
+    for (int c = 0; c < TS::NRA; ++c) {
+      const float x = __shfl(accb[0][(2 * c) & 3] + accb[0][((2 * c) & 3) + 1], m + 16 * (c >> 1));
+      bt[c] = (c < TS::NR && q == 0) ? x * scale : 0.f;
+    }
+    return;
+  }
   const int src = (m >> 2) << 4;
   const int rr = m & 3;
 #pragma unroll
@@ -2051,6 +2101,32 @@ struct SmemBytes<8, IMPLICIT> {  // W1: transposition buffer (the Gram's 192-wor
   static constexpr int value = (int)sizeof(float) * W1Lds::SIZE;
 };
 
+// LDS of launch 1 (gram_solve_kernel): as SmemBytes, except that the explicit
+// rank 33-64 rows are solved by the W1 block elimination, never by the panel solve
+// (launch 2, reduce_solve_kernel<4, false>, runs the panel solve and keeps SmemBytes).
+// They touch the Gram's staging words (columns | rating words), then W1LdsT<4>.
+// At most 10,240 B: 16 one-wave workgroups per CU (four waves per SIMD) fit in 160 KiB.
+constexpr int kPreStageWords = 128;
+template <int CN, bool IMPLICIT>
+struct FusedSmemBytes : SmemBytes<CN, IMPLICIT> {};
+template <>
+struct FusedSmemBytes<4, false> {
+  static constexpr int value =
+      (int)sizeof(float) * (W1LdsT<4>::SIZE > kPreStageWords ? W1LdsT<4>::SIZE : kPreStageWords);
+  static_assert(value >= (int)sizeof(float) * W1LdsT<4>::SIZE &&
+                    value >= (int)sizeof(float) * kPreStageWords && value % 16 == 0,
+                "rank 33-64 explicit: Gram staging and W1<4> solve");
+  static_assert(value <= 10240, "rank 33-64 explicit: 16 workgroups per CU");
+};
+// Waves per SIMD the launch-1 kernel is compiled for.  Rank 33-64 explicit: a row is a
+// latency chain (gathers, then 64 dependent pivots), covered by rows in flight, so it
+// is held to the 128 registers of four waves (one rhs tile, see RhsTiles).
+template <int CN, bool IMPLICIT>
+constexpr int kFusedWaves = IMPLICIT ? 2 : (CN == 4 ? 4 : 3);
+// Rank 33-64 explicit keeps its rhs sums in one accumulator tile.
+template <int CN>
+constexpr bool kOneRhsTile = CN == 4;
+
 __device__ __forceinline__ float shfl_xor_t(float v, int m) { return __shfl_xor(v, m); }
 __device__ __forceinline__ double shfl_xor_t(double v, int m) { return shfl_xor_f64(v, m); }
 
@@ -2201,10 +2277,12 @@ __device__ __forceinline__ void w1_finish_and_solve(floatx4 (&A)[NB * (NB + 1) /
 
 // (k <= 64 keeps one gather step in flight: two steps need 187 registers, i.e. two
 // waves per SIMD instead of three, measured slower on configs[1]: 2.07 -> 2.24 ms/iter.)
-// (Four waves per SIMD for explicit k <= 64 spill 49 registers: 2.76 vs 2.25 ms/iter;
-// round 5, after the lean sweep, 11 spills: 2.14 vs 2.02 ms/iter, profiles/r05/ab_occupancy.jsonl.)
+// (Four waves per SIMD for explicit k <= 64 with CN rhs tiles spill 49 registers: 2.76 vs
+// 2.25 ms/iter; round 5, after the lean sweep, 11 spills: 2.14 vs 2.02 ms/iter,
+// profiles/r05/ab_occupancy.jsonl, both at the panel's 12,288 B of LDS, i.e. still
+// three waves.  Rank 33-64 now fits four without spills: profiles/r09/occupancy4.md.)
 template <int CN, bool IMPLICIT>
-__global__ __launch_bounds__(64, IMPLICIT ? 2 : 3) void gram_solve_kernel(
+__global__ __launch_bounds__(64, (kFusedWaves<CN, IMPLICIT>)) void gram_solve_kernel(
     const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
     const float* __restrict__ val, const int32_t* __restrict__ light_rows,
     const int32_t* __restrict__ chunk_row, const int64_t* __restrict__ chunk_begin,
@@ -2214,7 +2292,7 @@ __global__ __launch_bounds__(64, IMPLICIT ? 2 : 3) void gram_solve_kernel(
     const float* __restrict__ scal, const uint32_t* __restrict__ Ysp, int32_t kp,
     int32_t zero_row, RescueList rl) {
   constexpr int NT = Cfg<CN>::NT;
-  __shared__ __attribute__((aligned(16))) unsigned char smem[SmemBytes<CN, IMPLICIT>::value];
+  __shared__ __attribute__((aligned(16))) unsigned char smem[FusedSmemBytes<CN, IMPLICIT>::value];
   floatx4 acc[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) acc[t] = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -2247,13 +2325,15 @@ __global__ __launch_bounds__(64, IMPLICIT ? 2 : 3) void gram_solve_kernel(
   } else {
     const int ey = split_exponent(scal[0]), er = split_exponent(scal[1]);
     inv2 = ldexpf(1.f, -2 * ey);
-    floatx4 accb[CN];
+    constexpr bool ONE = kOneRhsTile<CN>;
+    constexpr int NRT = RhsTiles<FullTiles<CN>, ONE>::N;
+    floatx4 accb[NRT];
 #pragma unroll
-    for (int c = 0; c < CN; ++c) accb[c] = floatx4{0.f, 0.f, 0.f, 0.f};
-    gram_accumulate_pre<FullTiles<CN>>(col, val, pb, pe, Ysp, (uint32_t)kp, zero_row,
-                                       ldexpf(1.f, er), (threadIdx.x & 15) * CN, acc, accb,
-                                       reinterpret_cast<int*>(smem), rmax);
-    rhs_from_tiles<FullTiles<CN>>(accb, ldexpf(1.f, -ey - er), bt);
+    for (int c = 0; c < NRT; ++c) accb[c] = floatx4{0.f, 0.f, 0.f, 0.f};
+    gram_accumulate_pre<FullTiles<CN>, ONE>(col, val, pb, pe, Ysp, (uint32_t)kp, zero_row,
+                                            ldexpf(1.f, er), (threadIdx.x & 15) * CN, acc, accb,
+                                            reinterpret_cast<int*>(smem), rmax);
+    rhs_from_tiles<FullTiles<CN>, ONE>(accb, ldexpf(1.f, -ey - er), bt);
     rmax *= ldexpf(1.f, er);
     if (chunk < 0 && (window_miss(diag_max_lane<CN>(acc), (float)(pe - pb), rmax) ||
                       rank_deficient_illcond<CN>(acc, inv2, pe - pb, k, reg))) {
@@ -2277,7 +2357,8 @@ __global__ __launch_bounds__(64, IMPLICIT ? 2 : 3) void gram_solve_kernel(
   if constexpr (!IMPLICIT && CN == 4) {
     // rank 33-64 explicit: the W1 block elimination on 4 x 4 tiles (swept diagonal
     // inverses + fp32 MFMA), in the Gram's scale
-    static_assert(W1LdsT<4>::SIZE <= PanelLds<4>::SIZE, "W1<4> LDS");
+    static_assert((int)sizeof(float) * W1LdsT<4>::SIZE <= FusedSmemBytes<4, false>::value,
+                  "W1<4> LDS");
     w1_finish_and_solve<false, 4, false>(acc, inv2, bt, n_reg, nullptr, smem, k, reg,
                                   X + (int64_t)row * ld, ld, row, rl);
   } else {

@@ -31,13 +31,16 @@ __device__ __forceinline__ void synth_spd(floatx4 (&acc)[NT], int nb) {
 }
 
 template <int NB, int MODE>
-__global__ __launch_bounds__(64, NB == 4 ? 3 : 1) void ablate_kernel(
+__global__ __launch_bounds__(64, NB == 4 ? (kFusedWaves<4, false>) : 1) void ablate_kernel(
     const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
     const float* __restrict__ val, const int32_t* __restrict__ rows,
     const uint32_t* __restrict__ Ysp, int kp, int zero_row, float sr, float inv2, float invb,
     float* __restrict__ X, int ld, int k, float reg, RescueList rl) {
   constexpr int NT = NB * (NB + 1) / 2;
-  __shared__ __attribute__((aligned(16))) unsigned char smem[SmemBytes<NB>::value];
+  // LDS and rhs tiles as the product kernels': gram_solve_kernel<4, false> / the W1 kernel
+  __shared__ __attribute__((aligned(16))) unsigned char smem[FusedSmemBytes<NB, false>::value];
+  constexpr bool ONE = NB == 4 && kOneRhsTile<4>;
+  constexpr int NRT = RhsTiles<FullTiles<NB>, ONE>::N;
   const int lane = threadIdx.x & 63;
   const int row = rows[blockIdx.x];
   const int64_t pb = row_ptr[row], pe = row_ptr[row + 1];
@@ -49,19 +52,19 @@ __global__ __launch_bounds__(64, NB == 4 ? 3 : 1) void ablate_kernel(
   if (MODE != 2) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) acc[t] = floatx4{0.f, 0.f, 0.f, 0.f};
-    floatx4 accb[NB];
+    floatx4 accb[NRT];
 #pragma unroll
-    for (int c = 0; c < NB; ++c) accb[c] = floatx4{0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < NRT; ++c) accb[c] = floatx4{0.f, 0.f, 0.f, 0.f};
     float rmax = 0.f;
     if constexpr (NB == 8)
       gram_accumulate_pre2<FullTiles<NB>>(col, val, pb, pe, Ysp, (uint32_t)kp, zero_row, sr,
                                           (lane & 15) * NB, acc, accb,
                                           reinterpret_cast<int*>(smem), rmax);
     else
-      gram_accumulate_pre<FullTiles<NB>>(col, val, pb, pe, Ysp, (uint32_t)kp, zero_row, sr,
-                                         (lane & 15) * NB, acc, accb,
-                                         reinterpret_cast<int*>(smem), rmax);
-    rhs_from_tiles<FullTiles<NB>>(accb, invb, bt);
+      gram_accumulate_pre<FullTiles<NB>, ONE>(col, val, pb, pe, Ysp, (uint32_t)kp, zero_row, sr,
+                                              (lane & 15) * NB, acc, accb,
+                                              reinterpret_cast<int*>(smem), rmax);
+    rhs_from_tiles<FullTiles<NB>, ONE>(accb, invb, bt);
   } else {
     synth_spd<NT>(acc, NB);
     bt[0] = 1.f;
