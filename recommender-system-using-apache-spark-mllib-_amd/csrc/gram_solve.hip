@@ -1955,6 +1955,8 @@ __device__ __forceinline__ bool w1_solve(floatx4 (&A)[NB * (NB + 1) / 2], float 
       if (d < ld) xrow[d] = (d < k && ok) ? xcol[c] : 0.f;
     }
   }
+  // a caller's ld may exceed k_pad = 16 NB (any ld >= k is allowed): those columns too
+  for (int d = 16 * NB + lane; d < ld; d += 64) xrow[d] = 0.f;
   return ok;
 }
 
@@ -2895,6 +2897,8 @@ __device__ __forceinline__ void dual_row(int row, int n, const int (&cj)[2],
         if (d < ld) *reinterpret_cast<float4*>(xrow + d) = make_float4(o[0], o[1], o[2], o[3]);
       }
   }
+  // ld past k_pad (any ld >= k is allowed): columns [KP, ld) are written as zero too
+  for (int d = KP + lane; d < ld; d += 64) xrow[d] = 0.f;
 }
 
 // One wavefront per short light row (the tail of the longest-first light list: every

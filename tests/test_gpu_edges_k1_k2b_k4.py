@@ -50,14 +50,26 @@ def _identity_index(n):
 N_COLS = 1000
 
 
+def _csr_cols_vals(nnz, seed):
+    assert nnz < (1 << 24)
+    cols = np.random.default_rng(seed).integers(0, N_COLS, nnz).astype(np.int32)
+    return cols, np.arange(nnz, dtype=np.float32)
+
+
+def _radix_rows(n_rows, nnz):
+    rng = np.random.default_rng(n_rows % 1000 + nnz)
+    rows = rng.integers(0, n_rows, nnz).astype(np.int32)
+    if nnz >= 2:  # the top row needs every key bit, the bottom one none
+        rows[rng.integers(0, nnz)] = n_rows - 1
+        rows[rng.integers(0, nnz)] = 0
+    return rows
+
+
 def _check_csr(rows, n_rows, seed):
     """als_csr_build of (rows, random cols, vals = position) vs O.csr_build, bit-exact.
     vals = arange(nnz) (exact in fp32 below 2^24) makes any mis-ordering visible."""
-    rng = np.random.default_rng(seed)
     nnz = len(rows)
-    assert nnz < (1 << 24)
-    cols = rng.integers(0, N_COLS, nnz).astype(np.int32)
-    vals = np.arange(nnz, dtype=np.float32)
+    cols, vals = _csr_cols_vals(nnz, seed)
     blk = E.build_block(_t(rows, torch.int32), _identity_index(n_rows), _t(cols, torch.int32),
                         _identity_index(N_COLS), _t(vals, torch.float32), E.Workspace(DEV))
     ptr_, idx_, val_ = O.csr_build(rows, cols, vals, n_rows)
@@ -75,12 +87,7 @@ def test_csr_radix_passes_and_tiles(n_rows, nnz):
     """bits = bit_length(n_rows - 1): 0 (one row), 8 (1 pass), 9 and 16 (2 passes), 17
     (3 passes), 25 (4 passes, most rows empty); nnz at the 4096-key tile boundaries and
     with a partial last wave."""
-    rng = np.random.default_rng(n_rows % 1000 + nnz)
-    rows = rng.integers(0, n_rows, nnz).astype(np.int32)
-    if nnz >= 2:  # the top row needs every key bit, the bottom one none
-        rows[rng.integers(0, nnz)] = n_rows - 1
-        rows[rng.integers(0, nnz)] = 0
-    _check_csr(rows, n_rows, seed=nnz)
+    _check_csr(_radix_rows(n_rows, nnz), n_rows, seed=nnz)
 
 
 def _stability_rows(pattern, nnz, n_rows):

@@ -222,6 +222,20 @@ def test_production_chunk_boundary(rank, implicit):
 SEGMENT_EARLY = (0, 1, 32, 33, 64, 65, 129, 130)
 
 
+def _two_segment_ratings(rank, implicit, n_src, cut, n):
+    """(early, dst, src, r): two rows of n ratings per entry of SEGMENT_EARLY, the first
+    early[j] of them from source ids below `cut`, plus one row rating every source id."""
+    rng = np.random.default_rng(100 + rank)
+    early = list(SEGMENT_EARLY) * 2
+    src = [np.concatenate([rng.choice(cut, e, replace=False),
+                           cut + rng.choice(n_src - cut, n - e, replace=False)]) for e in early]
+    src.append(np.arange(n_src))  # every source id rated: dense ids = ids, early ones first
+    dst = np.repeat(np.arange(len(src)), [len(s) for s in src]).astype(np.int32)
+    src = np.concatenate(src).astype(np.int32)
+    r = (rng.integers(1, 11, len(src)) / 2 - (2.5 if implicit else 0.0)).astype(np.float32)
+    return early, dst, src, r
+
+
 @pytest.mark.parametrize("implicit", [False, True])
 @pytest.mark.parametrize("rank", [16, 64, 128])
 def test_two_segment_edges(rank, implicit):
@@ -231,14 +245,7 @@ def test_two_segment_edges(rank, implicit):
     yet arrived source rows hold NaN during the early call.  Against the one-call solve
     and the fp64 oracle, with test_two_segment_half_sweep's bars."""
     n_src, cut, n, chunk, alpha = 512, 256, 130, 64, 2.0
-    rng = np.random.default_rng(100 + rank)
-    early = list(SEGMENT_EARLY) * 2
-    src = [np.concatenate([rng.choice(cut, e, replace=False),
-                           cut + rng.choice(n_src - cut, n - e, replace=False)]) for e in early]
-    src.append(np.arange(n_src))  # every source id rated: dense ids = ids, early ones first
-    dst = np.repeat(np.arange(len(src)), [len(s) for s in src]).astype(np.int32)
-    src = np.concatenate(src).astype(np.int32)
-    r = (rng.integers(1, 11, len(src)) / 2 - (2.5 if implicit else 0.0)).astype(np.float32)
+    early, dst, src, r = _two_segment_ratings(rank, implicit, n_src, cut, n)
     core = E.ALSCore(dst, src, r, device=DEV, chunk=chunk)
     assert core.iidx.n == n_src and core.uidx.n == len(early) + 1
     core.init_factors(rank, seed=7)

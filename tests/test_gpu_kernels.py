@@ -359,6 +359,18 @@ def _exact_rel_errs(x, ref):
     return e
 
 
+def _norm_spread_ratings():
+    """500 users x 300 items plus a second block of 400 users (ids 500 ..) who rate 120 items
+    of their own (ids 300 ..): with the second block's factors shrunk, those items' systems
+    see only tiny factor rows.  Light rows, dual-path short rows and one heavy item each."""
+    u1, i1, r1 = planted(500, 300, density=0.05, heavy_items=(3,), seed=31)
+    u2, i2, r2 = planted(400, 120, density=0.08, heavy_items=(5,), seed=32)  # tiny users' items
+    u = np.concatenate([u1, u2 + 500]).astype(np.int32)
+    i = np.concatenate([i1, i2 + 300]).astype(np.int32)
+    r = np.concatenate([r1, r2]).astype(np.float32)
+    return u, i, r
+
+
 @pytest.mark.parametrize("spread", [1e7, 1e9])
 @pytest.mark.parametrize("rank", [16, 48, 64, 100, 128])
 def test_split_window_row_norm_spread(spread, rank):
@@ -368,11 +380,7 @@ def test_split_window_row_norm_spread(spread, rank):
     items (light rows, dual-path short rows and one heavy, chunked item): those items'
     systems see only tiny factor rows and must still match the fp64 oracle to 1e-4
     per row — relative to their own norm — via the rescue launch."""
-    u1, i1, r1 = planted(500, 300, density=0.05, heavy_items=(3,), seed=31)
-    u2, i2, r2 = planted(400, 120, density=0.08, heavy_items=(5,), seed=32)  # tiny users' items
-    u = np.concatenate([u1, u2 + 500]).astype(np.int32)
-    i = np.concatenate([i1, i2 + 300]).astype(np.int32)
-    r = np.concatenate([r1, r2]).astype(np.float32)
+    u, i, r = _norm_spread_ratings()
     core = _core(u, i, r, chunk=128)
     core.init_factors(rank, seed=3)
     core.U[500:] /= spread
@@ -406,11 +414,7 @@ def test_rescue_list_emptied_between_row_chunks():
     length (scale word 2) after LAUNCH1..LAUNCH2 is the same in both calls, and 0 after
     RESCUE."""
     rank, spread = 64, 1e9
-    u1, i1, r1 = planted(500, 300, density=0.05, heavy_items=(3,), seed=31)
-    u2, i2, r2 = planted(400, 120, density=0.08, heavy_items=(5,), seed=32)
-    u = np.concatenate([u1, u2 + 500]).astype(np.int32)
-    i = np.concatenate([i1, i2 + 300]).astype(np.int32)
-    r = np.concatenate([r1, r2]).astype(np.float32)
+    u, i, r = _norm_spread_ratings()
     core = _core(u, i, r, chunk=128)
     core.init_factors(rank, seed=3)
     core.U[500:] /= spread

@@ -88,13 +88,15 @@ def _run(Qd, n_q, Vd, n_v, rank, top, lists, allow):
 
 # ------------------------------------------------------------------ 1. parity grid
 @functools.lru_cache(maxsize=None)
-def _grid(rank):
+def _grid_case(rank, n_q, n_v):
+    """N(0, 1) factors with one exact tie, a per-row exclusion list of seven kinds and three
+    allow masks; n_v >= 5 (the small sizes serve test_gpu_buffer_bounds.py)."""
     rng = np.random.default_rng(100 + rank)
-    n_q, n_v = 333, 1500
     Q = rng.standard_normal((n_q, rank)).astype(np.float32)
     Vm = rng.standard_normal((n_v, rank)).astype(np.float32)
-    Vm[10] = Vm[20]  # exact tie: the lower index first; 20 alone where 10 is excluded
-    top50, _ = O.topk(Q, Vm, 50)
+    lo, hi = (10, 20) if n_v > 20 else (1, n_v - 1)
+    Vm[lo] = Vm[hi]  # exact tie: the lower index first; hi alone where lo is excluded
+    top50, _ = O.topk(Q, Vm, min(50, n_v))
     lists = []
     for r in range(n_q):
         kind = r % 7
@@ -109,14 +111,19 @@ def _grid(rank):
         elif kind == 4:
             x = list(rng.integers(0, n_v, 40)) * 2 + [int(top50[r][0])] * 3  # duplicates
         elif kind == 5:
-            x = [0, n_v - 1] + list(rng.choice(np.arange(1, n_v - 1), 25, replace=False))
+            x = [0, n_v - 1] + list(rng.choice(np.arange(1, n_v - 1), min(25, n_v - 2),
+                                               replace=False))
         else:
-            x = [10] + list(top50[r][:3])                        # 10 excluded: 20 stands alone
+            x = [lo] + list(top50[r][:3])                        # lo excluded: hi stands alone
         lists.append([int(v) for v in x])
     S = Q.astype(np.float64) @ Vm.astype(np.float64).T
     allows = {"none": None, "half": rng.random(n_v) < 0.5, "five": np.zeros(n_v, bool)}
-    allows["five"][[3, 10, 20, 777, n_v - 1]] = True
+    allows["five"][[j for j in (3, 10, 20, 777, n_v - 1) if j < n_v]] = True
     return Q, Vm, S, lists, allows
+
+
+def _grid(rank):
+    return _grid_case(rank, 333, 1500)
 
 
 @pytest.mark.parametrize("allow", ["none", "half", "five"])
