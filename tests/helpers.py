@@ -261,3 +261,160 @@ def oracle_train_c(users, items, ratings, rank, iterations, reg, U0, implicit=Fa
         U, st = C.half_sweep(*up, V, reg, implicit=implicit, alpha=alpha)
         assert not st.any()
     return U, V, umap, imap, uids, iids
+
+
+# ---------------------------------------------------------------- K5 checks and the row-group cases
+def topk_check(Q, Vm, idx, sc, top, tol=1e-5):
+    """idx/sc vs the fp64 oracle: identical except where fp64 scores tie within tol."""
+    from oracle import als_oracle as O
+    ref_i, ref_s = O.topk(Q, Vm, top)
+    S = Q.astype(np.float64) @ Vm.astype(np.float64).T
+    for row in range(Q.shape[0]):
+        if not np.array_equal(idx[row], ref_i[row]):
+            bad = np.nonzero(idx[row] != ref_i[row])[0]
+            for p_ in bad:
+                assert abs(S[row, idx[row, p_]] - ref_s[row, p_]) <= tol * max(1, abs(ref_s[row, p_])), \
+                    (row, p_, idx[row, p_], ref_i[row, p_])
+        np.testing.assert_allclose(sc[row], ref_s[row], rtol=1e-5, atol=1e-5)
+    return ref_i, ref_s
+
+
+def topk_ref_ranking(S, adm, top):
+    """The reference lists of fp64 scores S under the admissibility mask adm: inadmissible
+    and NaN entries out, ranked by (score descending, index ascending), open slots
+    -1 / -inf."""
+    Sm = np.where(adm & ~np.isnan(S), S, -np.inf)
+    order = np.argsort(-Sm, axis=1, kind="stable")[:, :top]  # ties: lower index first
+    sc = np.take_along_axis(Sm, order, 1)
+    idx = np.where(np.isneginf(sc), -1, order)
+    if idx.shape[1] < top:
+        pad = top - idx.shape[1]
+        idx = np.pad(idx, ((0, 0), (0, pad)), constant_values=-1)
+        sc = np.pad(sc, ((0, 0), (0, pad)), constant_values=-np.inf)
+    return idx, sc
+
+
+def topk_ranking_check(idx, sc, S, adm, top, rows=None, skip=None):
+    """idx / sc: the kernel's lists of the rows of S / adm (all rows, or `rows` of them).
+    Returns the number of positions whose index differs from the reference's (each one
+    excused by the 1e-5 tie rule, or the check has failed); positions where both indices
+    are V rows of `skip` (bool [n_v]) are checked alike but not counted."""
+    ref_i, ref_s = topk_ref_ranking(S, adm, top)
+    excused = 0
+    for r in range(S.shape[0]):
+        n = int((ref_i[r] >= 0).sum())
+        assert (idx[r, n:] == -1).all() and np.isneginf(sc[r, n:]).all(), (r, n, idx[r], sc[r])
+        got = idx[r, :n]
+        assert (got >= 0).all() and len(set(got.tolist())) == n, (r, got)
+        assert adm[r, got].all(), f"row {r}: inadmissible row listed: {got[~adm[r, got]]}"
+        for p in np.nonzero(got != ref_i[r, :n])[0]:  # only where fp64 scores tie within 1e-5
+            assert abs(S[r, got[p]] - ref_s[r, p]) <= 1e-5 * max(1, abs(ref_s[r, p])), (r, p)
+            excused += not (skip is not None and skip[got[p]] and skip[ref_i[r, p]])
+        np.testing.assert_allclose(sc[r, :n], ref_s[r, :n], rtol=1e-5, atol=1e-5)
+    return excused
+
+
+def topk_sample_check(idx, sc, S, top, adm=None, skip=None):
+    """topk_ranking_check on whole arrays (the same assertions, no loop over the rows), for
+    the samples of test_gpu_topk_row_groups.py.  Returns {"positions": listed positions of
+    the reference, "excused": those whose index differs from the reference's under the
+    1e-5 tie rule (outside `skip`, as above), "max_score_err": the largest
+    |score - ref| / max(1, |ref|)}."""
+    n_r, n_v = S.shape
+    if adm is None:
+        adm = np.ones(S.shape, bool)
+    ref_i, ref_s = topk_ref_ranking(S, adm, top)
+    real = ref_i >= 0
+    assert (idx[~real] == -1).all() and np.isneginf(sc[~real]).all(), \
+        np.nonzero((~real & ((idx != -1) | ~np.isneginf(sc))).any(1))[0][:10]
+    assert (idx[real] >= 0).all() and (idx[real] < n_v).all(), \
+        np.nonzero((real & ((idx < 0) | (idx >= n_v))).any(1))[0][:10]
+    # distinct per row (open slots get distinct negative stand-ins)
+    srt = np.sort(np.where(real, idx, -1 - np.arange(top)[None, :]), axis=1)
+    assert (srt[:, 1:] != srt[:, :-1]).all(), np.nonzero((srt[:, 1:] == srt[:, :-1]).any(1))[0][:10]
+    got = np.where(real, idx, 0).astype(np.int64)
+    rr = np.arange(n_r)[:, None]
+    assert adm[rr, got][real].all(), "an inadmissible row is listed"
+    bad = real & (idx != ref_i)
+    refs = np.where(real, ref_s, 0.0)
+    scale = np.maximum(1.0, np.abs(refs))
+    off = np.abs(S[rr, got] - refs)
+    assert (off[bad] <= 1e-5 * scale[bad]).all(), \
+        [(int(r), int(p), int(idx[r, p]), int(ref_i[r, p])) for r, p in
+         zip(*np.nonzero(bad & (off > 1e-5 * scale)))][:10]
+    np.testing.assert_allclose(sc[real], ref_s[real], rtol=1e-5, atol=1e-5)
+    if skip is not None:
+        bad &= ~(skip[got] & skip[np.where(real, ref_i, 0)])
+    err = np.abs(np.where(real, sc, 0.0).astype(np.float64) - refs) / scale
+    return {"positions": int(real.sum()), "excused": int(bad.sum()),
+            "max_score_err": float(err.max()) if err.size else 0.0}
+
+
+# The two-row-group cases of K5 (test_gpu_topk_row_groups.py, test_topk_row_groups_cpu.py).
+# csrc/topk.hip's topk_split_rg takes two row groups (256 query rows per workgroup) for
+# register lists and key logs from kTkRg2MinRows = 262,144 query rows; a key-log launch
+# covers kTkLogBlocks = 512 blocks, 131,072 rows at two groups.
+K5RG_MIN_ROWS = 262144
+K5RG_SLICE_ROWS = 131072
+K5RG_NQ = K5RG_MIN_ROWS + 130   # 1,025 blocks; the last: group 0 full, 2 rows of group 1
+K5RG_NV = 1159                  # 3 x 384 + 7 = 6 x 192 + 7
+K5RG_RANKS = (24, 40, 100)      # NK = 1, 2, 4
+K5RG_TOPS = (8, 11, 16, 17, 64, 99, 128)  # TOPR 8 / 12 / 16 / 32 / 64 / 100 / 128
+K5RG_FILTERED = tuple((k, t) for k in (40, 100) for t in (11, 17, 99))
+K5RG_SPLIT = K5RG_SLICE_ROWS + 65   # the one-group calls: rows [0, SPLIT) and [SPLIT, n_q)
+K5RG_BIG_ROWS = (0, K5RG_SPLIT)     # Q[row, 0] = K5RG_BIG: max |Q| of the call and of each half
+K5RG_BIG = 6.0
+K5RG_ZERO_ROWS = (200, 300, K5RG_SLICE_ROWS + 130, K5RG_NQ - 1)  # 200: group 1, 300: group 0
+K5RG_TIE = (10, 1100)               # Vm[1100] = Vm[10]
+K5RG_COPIES = 300
+K5RG_EXCUSED_CAP = 0.005            # share of sampled positions the tie rule may excuse
+K5RG_WINDOW_CAP = 0.0015            # ... and what random data of these shapes can offer it
+
+_K5RG_ITEMS = {}
+
+
+def k5rg_items(rank):
+    """(Vm [K5RG_NV, rank] float32, copies): N(0, 1) rows times uniform(0.2, 2.0), the
+    exact-tie pair K5RG_TIE, and K5RG_COPIES exact copies of one strong row (3 x a N(0, 1)
+    row) at the sorted indices `copies`, scattered over the index range."""
+    if rank not in _K5RG_ITEMS:
+        rng = np.random.default_rng(5000 + rank)
+        Vm = rng.standard_normal((K5RG_NV, rank)).astype(np.float32)
+        Vm *= rng.uniform(0.2, 2.0, (K5RG_NV, 1)).astype(np.float32)
+        lo, hi = K5RG_TIE
+        ends = [3, K5RG_NV - 2]  # one in the first tile, one in the ragged last tile
+        free = np.setdiff1d(np.arange(K5RG_NV), [lo, hi] + ends)
+        copies = np.sort(np.concatenate([ends, rng.choice(free, K5RG_COPIES - 2, replace=False)]))
+        Vm[copies] = 3.0 * rng.standard_normal(rank).astype(np.float32)
+        Vm[lo] = 1.75 * rng.standard_normal(rank).astype(np.float32)  # (strong enough to be listed)
+        Vm[hi] = Vm[lo]
+        Vm.setflags(write=False)
+        copies.setflags(write=False)
+        _K5RG_ITEMS[rank] = (Vm, copies)
+    return _K5RG_ITEMS[rank]
+
+
+def k5rg_sample_rows(n_q=K5RG_NQ, seam=K5RG_SLICE_ROWS):
+    """The rows compared with fp64: the first 512 (two workgroups), the launch seam of the
+    key-log path +- 256, the last 400 and 300 drawn ones (sorted, unique)."""
+    drawn = np.random.default_rng(77).choice(n_q, 300, replace=False)
+    return np.unique(np.concatenate([np.arange(512), np.arange(seam - 256, seam + 257),
+                                     np.arange(n_q - 400, n_q), drawn]))
+
+
+def k5rg_scores(Q, Vm, copies):
+    """fp64 Q Vm^T with the planted ties exact by construction: bit-identical fp32 rows
+    have one true score, whatever the matrix product's blocking makes of the columns."""
+    S = Q.astype(np.float64) @ Vm.astype(np.float64).T
+    S[:, copies[1:]] = S[:, copies[:1]]
+    S[:, K5RG_TIE[1]] = S[:, K5RG_TIE[0]]
+    return S
+
+
+def k5rg_window_share(S, top, planted):
+    """Share of the top `top` positions of each row of S whose fp64 score lies within the
+    1e-5 tie window of the next one down (top + 1 scores per row; the planted columns left
+    out): the most the tie rule could excuse on such data."""
+    s = -np.sort(-S[:, ~planted], axis=1)[:, :top + 1]
+    close = (s[:, :-1] - s[:, 1:]) <= 1e-5 * np.maximum(1.0, np.abs(s[:, :-1]))
+    return float(close.mean())

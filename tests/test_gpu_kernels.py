@@ -21,6 +21,7 @@ import torch
 import als_mi355x.engine as E
 from oracle import als_oracle as O
 from helpers import planted, rel_row_err, rel_row_errs, report
+from helpers import topk_check as _topk_check
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -894,20 +895,6 @@ def test_topk_fewer_items_than_top(n_v, top):
     assert np.all(np.sort(idx[:, :n_v], axis=1) == np.arange(n_v))
     ref_i, ref_s = O.topk(Q.cpu().numpy(), Vm.cpu().numpy(), n_v)
     np.testing.assert_allclose(sc[:, :n_v], ref_s, rtol=1e-5, atol=1e-5)
-
-
-def _topk_check(Q, Vm, idx, sc, top, tol=1e-5):
-    """idx/sc vs the fp64 oracle: identical except where fp64 scores tie within tol."""
-    ref_i, ref_s = O.topk(Q, Vm, top)
-    S = Q.astype(np.float64) @ Vm.astype(np.float64).T
-    for row in range(Q.shape[0]):
-        if not np.array_equal(idx[row], ref_i[row]):
-            bad = np.nonzero(idx[row] != ref_i[row])[0]
-            for p_ in bad:
-                assert abs(S[row, idx[row, p_]] - ref_s[row, p_]) <= tol * max(1, abs(ref_s[row, p_])), \
-                    (row, p_, idx[row, p_], ref_i[row, p_])
-        np.testing.assert_allclose(sc[row], ref_s[row], rtol=1e-5, atol=1e-5)
-    return ref_i, ref_s
 
 
 def _topk_dev(Q, Vm, rank, top):

@@ -15,6 +15,7 @@ import torch
 
 from als_mi355x import engine as E
 from als_mi355x import filters as F
+from helpers import topk_ranking_check as _check  # the reference ranking of the docstring
 from oracle import als_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -51,32 +52,6 @@ def _admissible(n_q, n_v, lists, allow):
 def _bits(allow):
     return None if allow is None else F.pack_allow_bits(
         torch.as_tensor(np.nonzero(allow)[0]).to(DEV), len(allow))
-
-
-def _ref(S, adm, top):
-    Sm = np.where(adm & ~np.isnan(S), S, -np.inf)
-    order = np.argsort(-Sm, axis=1, kind="stable")[:, :top]  # ties: lower index first
-    sc = np.take_along_axis(Sm, order, 1)
-    idx = np.where(np.isneginf(sc), -1, order)
-    if idx.shape[1] < top:
-        pad = top - idx.shape[1]
-        idx = np.pad(idx, ((0, 0), (0, pad)), constant_values=-1)
-        sc = np.pad(sc, ((0, 0), (0, pad)), constant_values=-np.inf)
-    return idx, sc
-
-
-def _check(idx, sc, S, adm, top, rows=None):
-    """idx / sc: the kernel's lists of the rows of S / adm (all rows, or `rows` of them)."""
-    ref_i, ref_s = _ref(S, adm, top)
-    for r in range(S.shape[0]):
-        n = int((ref_i[r] >= 0).sum())
-        assert (idx[r, n:] == -1).all() and np.isneginf(sc[r, n:]).all(), (r, n, idx[r], sc[r])
-        got = idx[r, :n]
-        assert (got >= 0).all() and len(set(got.tolist())) == n, (r, got)
-        assert adm[r, got].all(), f"row {r}: inadmissible row listed: {got[~adm[r, got]]}"
-        for p in np.nonzero(got != ref_i[r, :n])[0]:  # only where fp64 scores tie within 1e-5
-            assert abs(S[r, got[p]] - ref_s[r, p]) <= 1e-5 * max(1, abs(ref_s[r, p])), (r, p)
-        np.testing.assert_allclose(sc[r, :n], ref_s[r, :n], rtol=1e-5, atol=1e-5)
 
 
 def _run(Qd, n_q, Vd, n_v, rank, top, lists, allow):
