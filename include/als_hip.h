@@ -648,6 +648,87 @@ int als_list_similarity(const float* V, int64_t n_v, int32_t ld, int32_t k,
                         const int32_t* idx, int64_t n_q, int32_t m,
                         double* out, void* stream);
 
+/* ---- K15: the lists of all users together (catalogue coverage, Herlocker et al. 2004;
+ *      novelty and personalisation, Zhou et al. 2010; average popularity and long-tail
+ *      share, Abdollahpouri et al.).  Replaces nothing in Spark, which has none of these;
+ *      the reference only filters by popularity, RecommenderSystem.py:245 ------------------ */
+
+/* Added under ABI 9 without a version bump: six new symbols only, nothing existing changes.
+ * Lists, for all three calls: idx int32 [n_q, idx_ld], the layout als_topk* / als_diversify
+ * write; only the first `at` positions of a row count (1 <= at <= 256, idx_ld >= at; what
+ * lies past them is never read).  An entry is VALID when 0 <= idx < n_v and, when allow_bits
+ * is given (als_topk_filtered's mask: ceil(n_v / 32) words, bits past n_v ignored), its bit
+ * is set; the catalogue is then the allowed rows only.  Every other entry is skipped: the -1
+ * of an open slot, an id the model does not know, a row outside the catalogue.  Duplicates
+ * inside one list each count (K5 never writes any; the overlap identity below assumes none).
+ *
+ * als_list_exposure: counts[j] (int32 [n_v]) = the valid entries naming row j.  accumulate
+ * != 0 adds to what counts and *n_skipped_dev hold, so lists can be fed in chunks;
+ * accumulate == 0 overwrites both in full, rows nobody lists included.  n_skipped_dev
+ * (int64, nullable) = the skipped entries among the n_q * at.  Integer adds only: the counts
+ * are exact and bit-identical run to run whatever order the adds land in.  Each workgroup
+ * keeps als_list_exposure_window() int32 counters in LDS as a direct-mapped cache of the
+ * catalogue (row j in slot j mod window, first row to arrive owns the slot; a row that finds
+ * its slot taken is added in memory) and adds its non-zero slots to counts once at the end,
+ * so with n_v <= window nothing but those final adds reaches memory, and in a larger skewed
+ * catalogue the rows that take most entries are summed on chip.  No workspace.  The total
+ * per row must fit int32.
+ *
+ * als_list_concentration: n = the catalogue rows (n_v, or the set bits below n_v), c_j their
+ * counts (a negative count reads as 0), T = sum c_j.  out[7], fp64:
+ *   out[0] n                           out[1] rows with c_j > 0 (coverage = out[1] / out[0])
+ *   out[2] T                           out[5] sum_j c_j (c_j - 1) / 2
+ *   out[3] Gini index of exposure, sum_{j=1..n} (2j - n - 1) c_(j) / (n T) over the ascending
+ *          counts: 0 when every row is listed equally often, 1 - 1/n when one row takes
+ *          everything; NaN when T = 0
+ *   out[4] Shannon entropy in bits, -sum_{c_j > 0} (c_j / T) log2(c_j / T); NaN when T = 0
+ *   out[6] max_j c_j
+ * out[5] counts the (pair of lists, shared row) incidences of duplicate-free lists, so
+ * personalisation = 1 - out[5] / (C(n_lists, 2) at), formed by the caller; n_lists and at
+ * are only checked.  The counts are sorted by the library's radix sort with rows outside the
+ * catalogue keyed 0: zeros add nothing to the Gini sum, and a non-zero count's catalogue rank
+ * is its rank in the full sort minus n_v - n.  All sums are fp64 in a fixed order (per-block
+ * partials in row order, then in sorted order, each folded by one block): two calls give
+ * identical bits, and every value is exact while it stays below 2^53.  n_v == 0 writes
+ * {0, 0, 0, NaN, NaN, 0, 0}.
+ *
+ * als_list_novelty: pop int32 [n_v] = how often each row was rated (a RatingBlock's
+ * row-pointer differences), n_pop = the rows of the listing side, tail_bits (nullable, the
+ * form of allow_bits) = the long-tail rows.  One wavefront per list; over the valid entries
+ * of row r in position order, in fp64:
+ *   novelty_r  mean of log2(n_pop / pop_j) over the entries with pop_j > 0 (mean
+ *              self-information in bits); NaN without such an entry
+ *   arp_r      mean of pop_j over all valid entries; NaN without a valid entry
+ *   tail_r     share of the valid entries whose bit is set in tail_bits; NaN when tail_bits
+ *              is NULL or the row has no valid entry
+ * sums_out[7] = { sum novelty_r, rows with a novelty, sum arp_r, rows with a valid entry,
+ * sum tail_r, valid entries, skipped entries }; a NaN row adds nothing and is not counted.
+ * per_row_out: NULL or f64 [n_q, 3] = novelty_r, arp_r, tail_r.  Fixed summation order (rows
+ * per wave in row order, waves in wave order, blocks by one final block): two calls give
+ * bit-identical output.
+ *
+ * All three, checked on the host before any launch: at outside [1, 256] is
+ * ALS_EUNSUPPORTED; negative sizes, idx_ld < at, n_v >= 2^31 - 1, n_pop < 1, null pointers
+ * (when the sizes are non-zero) and a workspace that is not 16-byte aligned are ALS_EINVAL;
+ * a short workspace is ALS_EWORKSPACE.  n_q == 0 is defined: the counts are zeroed unless
+ * accumulating, the sums are zeroed.  The two workspaces (16-byte aligned) are sized by
+ * als_list_concentration_scratch_bytes(n_v) (0 for an n_v the call rejects) and
+ * als_list_novelty_scratch_bytes(n_q).  Costs beside K5 and beside torch.bincount: DESIGN.md
+ * section K15. */
+int32_t als_list_exposure_window(void);
+int als_list_exposure(const int32_t* idx, int64_t n_q, int32_t idx_ld, int32_t at, int64_t n_v,
+                      const uint32_t* allow_bits, int accumulate, int32_t* counts,
+                      int64_t* n_skipped_dev, void* stream);
+size_t als_list_concentration_scratch_bytes(int64_t n_v);
+int als_list_concentration(const int32_t* counts, int64_t n_v, const uint32_t* allow_bits,
+                           int64_t n_lists, int32_t at, double* out, void* ws, size_t ws_bytes,
+                           void* stream);
+size_t als_list_novelty_scratch_bytes(int64_t n_q);
+int als_list_novelty(const int32_t* idx, int64_t n_q, int32_t idx_ld, int32_t at, int64_t n_v,
+                     const uint32_t* allow_bits, const int32_t* pop, int64_t n_pop,
+                     const uint32_t* tail_bits, double* sums_out, double* per_row_out,
+                     void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,6 +102,12 @@ SIGNATURES = {
                                      I32, P, I32, P, P, P, SZ, P]),
     "als_diversify": (ctypes.c_int, [P, I64, I32, I32, P, P, I64, I32, I32, F32, P, P, P, P]),
     "als_list_similarity": (ctypes.c_int, [P, I64, I32, I32, P, I64, I32, P, P]),
+    "als_list_exposure_window": (I32, []),
+    "als_list_exposure": (ctypes.c_int, [P, I64, I32, I32, I64, P, ctypes.c_int, P, P, P]),
+    "als_list_concentration_scratch_bytes": (SZ, [I64]),
+    "als_list_concentration": (ctypes.c_int, [P, I64, P, I64, I32, P, P, SZ, P]),
+    "als_list_novelty_scratch_bytes": (SZ, [I64]),
+    "als_list_novelty": (ctypes.c_int, [P, I64, I32, I32, I64, P, P, I64, P, P, P, P, SZ, P]),
 }
 
 ABI_VERSION = 9

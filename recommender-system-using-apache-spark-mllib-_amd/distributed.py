@@ -46,7 +46,8 @@ import torch.distributed as dist
 from .engine import id_offset
 from .filters import (reject_sharded_diversify, reject_sharded_explain, reject_sharded_filters,
                       reject_sharded_fold_in,
-                      reject_sharded_full_rank, reject_sharded_nonnegative,
+                      reject_sharded_full_rank, reject_sharded_list_metrics,
+                      reject_sharded_nonnegative,
                       reject_sharded_objective, reject_sharded_regression,
                       reject_sharded_similar)
 
@@ -983,6 +984,18 @@ class ShardedALS:
     def list_similarity(self, id_lists, user_side: bool = True):
         """ALSCore.list_similarity is not offered on the sharded engine yet."""
         reject_sharded_diversify(sharded_engine=True)
+
+    def list_metrics(self, id_lists=None, *, top=None, user_side: bool = True, exclude=None,
+                     candidates=None, popularity=None, head_fraction: float = 0.2,
+                     per_row: bool = False) -> dict:
+        """ALSCore.list_metrics is not offered on the sharded engine yet."""
+        reject_sharded_list_metrics()
+
+    def _list_metrics_of_rows(self, rows, user_side: bool = True, *, candidates=None,
+                             popularity=None, head_fraction: float = 0.2,
+                             per_row: bool = False) -> dict:
+        """list_metrics for lists given as dense rows: refused like list_metrics."""
+        reject_sharded_list_metrics()
 
     def regression_metrics(self, users, items, ratings, through_origin: bool = False) -> dict:
         """ALSCore.regression_metrics is not offered on the sharded engine yet."""

@@ -800,6 +800,192 @@ def list_similarity_rows(idx: torch.Tensor, V: torch.Tensor, n_v: int, rank: int
     return out
 
 
+# ---------------------------------------------------------------------------
+# K15: the lists of all rows together (exposure, concentration, popularity)
+# ---------------------------------------------------------------------------
+LIST_MAX_AT = 256  # als_list_exposure / als_list_novelty: list positions read per row
+LIST_METRIC_FIELDS = ("coverage", "gini", "entropy", "effectiveItems", "personalization",
+                      "topItemShare", "novelty", "averagePopularity", "longTailShare", "lists",
+                      "entries", "skipped")
+
+
+def _list_rows_args(idx, at, who: str):
+    """(n_q, idx_ld, at) of a list matrix for the K15 calls; raises before the library is
+    touched."""
+    if (not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32 or idx.dim() != 2
+            or (idx.shape[1] > 1 and idx.stride(1) != 1)):
+        raise ValueError(f"{who}: idx must be an int32 [n_q, width] tensor with unit stride "
+                         "along a row")
+    at = int(at)
+    if not 1 <= at <= LIST_MAX_AT:
+        raise ValueError(f"{who}: at must be in [1, {LIST_MAX_AT}], got {at}")
+    if idx.shape[1] < at:
+        raise ValueError(f"{who}: lists of width {idx.shape[1]} < at = {at}")
+    n_q = int(idx.shape[0])
+    ld = int(idx.stride(0)) if n_q > 1 else int(idx.shape[1])  # one row: any stride
+    return n_q, ld, at
+
+
+def list_exposure_window() -> int:
+    """Rows per LDS counter window of als_list_exposure (0: the kernel keeps none)."""
+    return int(_lib.lib().als_list_exposure_window())
+
+
+def list_exposure_rows(idx: torch.Tensor, at: int, n_v: int, allow_bits=None, *, counts=None,
+                       skipped=None):
+    """K15 (als_list_exposure) over the lists idx (int32 [n_q, >= at], dense rows): how often
+    each of the n_v rows is named in the first `at` positions.  An entry outside [0, n_v) —
+    the -1 of an open slot — or with its bit clear in allow_bits (filters.pack_allow_bits;
+    None: every row) is skipped.  Returns (counts int32 [n_v], skipped int64 [1]), both on
+    the device; given `counts` (and `skipped`) from an earlier call, the new lists are added
+    to them, so lists can be fed in chunks.  Integer adds: exact, and the same bits every
+    run."""
+    n_q, ld, at = _list_rows_args(idx, at, "list_exposure_rows")
+    n_v = int(n_v)
+    if n_v < 0:
+        raise ValueError("list_exposure_rows: n_v must be >= 0")
+    accumulate = counts is not None
+    if accumulate and (counts.dtype != torch.int32 or counts.numel() != n_v
+                       or not counts.is_contiguous()):
+        raise ValueError(f"list_exposure_rows: counts must be a contiguous int32 [{n_v}] tensor")
+    if skipped is not None and not accumulate:
+        raise ValueError("list_exposure_rows: skipped= continues an earlier call: pass its "
+                         "counts too")
+    L = _lib.lib()
+    dev = idx.device
+    if counts is None:
+        counts = torch.empty(n_v, dtype=torch.int32, device=dev)
+    if skipped is None:
+        skipped = torch.zeros(1, dtype=torch.int64, device=dev)
+    check(L.als_list_exposure(ptr(idx), n_q, ld, at, n_v, ptr(allow_bits), int(accumulate),
+                              ptr(counts), ptr(skipped), stream_ptr(dev)), "als_list_exposure")
+    return counts, skipped
+
+
+def list_concentration(counts: torch.Tensor, n_v: int, allow_bits, n_lists: int, at: int,
+                       ws: Workspace) -> torch.Tensor:
+    """K15 (als_list_concentration): f64 [7] on the device = catalogue rows, rows listed, total,
+    Gini index, Shannon entropy (bits), pair overlap sum c (c - 1) / 2, largest count, over the
+    counts of the catalogue rows (every row, or those set in allow_bits).  Gini and entropy are
+    NaN when nothing is listed."""
+    n_v = int(n_v)
+    if counts.dtype != torch.int32 or counts.numel() != n_v or not counts.is_contiguous():
+        raise ValueError(f"list_concentration: counts must be a contiguous int32 [{n_v}] tensor")
+    if not 1 <= int(at) <= LIST_MAX_AT:
+        raise ValueError(f"list_concentration: at must be in [1, {LIST_MAX_AT}], got {at}")
+    L = _lib.lib()
+    dev = counts.device
+    out = torch.empty(7, dtype=torch.float64, device=dev)
+    w = ws.get(L.als_list_concentration_scratch_bytes(n_v))
+    check(L.als_list_concentration(ptr(counts), n_v, ptr(allow_bits), int(n_lists), int(at),
+                                   ptr(out), ptr(w), w.numel(), stream_ptr(dev)),
+          "als_list_concentration")
+    return out
+
+
+def list_novelty_rows(idx: torch.Tensor, at: int, n_v: int, pop: torch.Tensor, n_pop: int,
+                      ws: Workspace, allow_bits=None, tail_bits=None, per_row: bool = False):
+    """K15 (als_list_novelty) over the lists idx (as list_exposure_rows): pop int32 [n_v] = how
+    often each row was rated, n_pop = rows of the listing side, tail_bits = the long-tail rows
+    (the form of allow_bits; None: no long-tail share).  Returns (sums f64 [7] = sum of row
+    novelty (mean log2(n_pop / pop) over the entries with pop > 0), rows with one, sum of row
+    mean popularity, rows with a valid entry, sum of row long-tail share, valid entries, skipped
+    entries; per-row f64 [n_q, 3] = novelty, mean popularity, long-tail share with NaN where
+    undefined, or None)."""
+    n_q, ld, at = _list_rows_args(idx, at, "list_novelty_rows")
+    n_v = int(n_v)
+    if pop.dtype != torch.int32 or pop.numel() != n_v or not pop.is_contiguous():
+        raise ValueError(f"list_novelty_rows: pop must be a contiguous int32 [{n_v}] tensor")
+    if int(n_pop) < 1:
+        raise ValueError(f"list_novelty_rows: n_pop must be >= 1, got {n_pop}")
+    L = _lib.lib()
+    dev = idx.device
+    out = torch.empty(7, dtype=torch.float64, device=dev)
+    rows = torch.empty((n_q, 3), dtype=torch.float64, device=dev) if per_row else None
+    w = ws.get(L.als_list_novelty_scratch_bytes(n_q))
+    check(L.als_list_novelty(ptr(idx), n_q, ld, at, n_v, ptr(allow_bits), ptr(pop), int(n_pop),
+                             ptr(tail_bits), ptr(out), ptr(rows), ptr(w), w.numel(),
+                             stream_ptr(dev)), "als_list_novelty")
+    return out, rows
+
+
+def long_tail_bits(pop: torch.Tensor, n_v: int, head_fraction: float, cat_rows=None):
+    """The long tail as a bit mask (filters.pack_allow_bits): every catalogue row (cat_rows,
+    ascending dense rows; None: all n_v) outside the floor(head_fraction * n) most-rated ones,
+    n = the catalogue's size.  Rows rated equally often at the cut go to the head by ascending
+    row (one stable torch.sort)."""
+    head_fraction = float(head_fraction)
+    if not 0.0 < head_fraction < 1.0:
+        raise ValueError(f"head_fraction must be inside (0, 1), got {head_fraction}")
+    n_v = int(n_v)
+    if cat_rows is None:
+        cat_rows = torch.arange(n_v, device=pop.device)
+    cat_rows = cat_rows.long()
+    n_head = int(math.floor(head_fraction * int(cat_rows.numel())))
+    order = torch.sort(pop[cat_rows].long(), descending=True, stable=True).indices
+    return _filters.pack_allow_bits(cat_rows[order[n_head:]], n_v)
+
+
+def list_metrics_dict(conc, nov, n_lists: int, at: int, skipped: int = 0,
+                      tail: bool = True) -> dict:
+    """K15's raw sums (host lists: als_list_concentration's 7, als_list_novelty's 7 or None
+    when no popularity is known) as the beyond-accuracy measures of n_lists lists of `at`
+    slots:
+      coverage          catalogue rows listed at least once / catalogue rows
+      gini, entropy     of the exposure counts (entropy in bits); effectiveItems = 2 ** entropy
+      personalization   1 - mean overlap of two lists = 1 - pairs / (C(n_lists, 2) at);
+                        NaN under two lists
+      topItemShare      the share of the lists that name the most listed row
+      novelty           mean over the lists of the mean log2(n_pop / popularity)
+      averagePopularity mean over the lists of the mean popularity of what they name
+      longTailShare     mean over the lists of the share of long-tail rows
+      lists, entries (valid ones), skipped (open slots, unknown ids, rows off the catalogue)
+    The three popularity fields are NaN without `nov` (longTailShare also with tail=False)."""
+    nan = float("nan")
+
+    def ratio(a, b):
+        return a / b if b > 0 else nan
+    n_lists, at = int(n_lists), int(at)
+    pairs = n_lists * (n_lists - 1) // 2
+    entropy = conc[4]
+    out = {"coverage": ratio(conc[1], conc[0]), "gini": conc[3], "entropy": entropy,
+           "effectiveItems": 2.0 ** entropy if entropy == entropy else nan,
+           "personalization": 1.0 - conc[5] / (pairs * at) if pairs > 0 else nan,
+           "topItemShare": ratio(conc[6], n_lists),
+           "novelty": nan, "averagePopularity": nan, "longTailShare": nan,
+           "lists": n_lists, "entries": int(conc[2]), "skipped": int(skipped)}
+    if nov is not None:
+        out["novelty"] = ratio(nov[0], nov[1])
+        out["averagePopularity"] = ratio(nov[2], nov[3])
+        if tail:
+            out["longTailShare"] = ratio(nov[4], nov[3])
+        out["skipped"] = int(nov[6])
+    return out
+
+
+def list_metrics_rows(rows: torch.Tensor, at: int, n_v: int, ws: Workspace, *, allow_bits=None,
+                      cat_rows=None, pop=None, n_pop=None, head_fraction: float = 0.2,
+                      per_row: bool = False):
+    """The three K15 calls over one list matrix (int32 [n, >= at] dense rows) and
+    list_metrics_dict of their sums.  allow_bits / cat_rows: the catalogue as a mask and as
+    ascending rows (both None: all n_v rows).  pop / n_pop as list_novelty_rows; without pop
+    the popularity fields are NaN.  Returns (dict, per-row f64 [n, 3] or None)."""
+    n, _, at = _list_rows_args(rows, at, "list_metrics_rows")
+    head_fraction = float(head_fraction)
+    if not 0.0 < head_fraction < 1.0:
+        raise ValueError(f"head_fraction must be inside (0, 1), got {head_fraction}")
+    counts, skipped = list_exposure_rows(rows, at, n_v, allow_bits)
+    conc = list_concentration(counts, n_v, allow_bits, n, at, ws)
+    nov = pr = None
+    if pop is not None:
+        tail = long_tail_bits(pop, n_v, head_fraction, cat_rows)
+        nov, pr = list_novelty_rows(rows, at, n_v, pop, n_pop, ws, allow_bits, tail, per_row)
+        nov = nov.tolist()
+    elif per_row:
+        pr = torch.full((n, 3), float("nan"), dtype=torch.float64, device=rows.device)
+    return list_metrics_dict(conc.tolist(), nov, n, at, int(skipped.item())), pr
+
+
 MAX_RANK_AT = 256  # als_rank_metrics: list positions scored per row
 
 
@@ -1503,6 +1689,101 @@ class ALSCore:
             raise ValueError(f"id_lists must be [n, m], got shape {tuple(lists.shape)}")
         rows = oi.rows_of(lists).to(torch.int32)
         return list_similarity_rows(rows, Vo, oi.n, self.rank)
+
+    # ---- K15: do all rows get the same few blockbusters? ----
+    def popularity(self, user_side: bool = True):
+        """How often each row of the OTHER side was rated (int32 [n], dense order): the
+        row-pointer differences of its rating block, no pass over the ratings.  None on a
+        core built from saved factors."""
+        block = self.item_block if user_side else self.user_block
+        if block is None:
+            return None
+        return (block.row_ptr[1:] - block.row_ptr[:-1]).to(torch.int32).contiguous()
+
+    def list_metrics(self, id_lists=None, *, top=None, user_side: bool = True, exclude=None,
+                     candidates=None, popularity=None, head_fraction: float = 0.2,
+                     per_row: bool = False) -> dict:
+        """The lists of ALL rows looked at together (K15): {"coverage", "gini", "entropy",
+        "effectiveItems", "personalization", "topItemShare", "novelty", "averagePopularity",
+        "longTailShare", "lists", "entries", "skipped"} as list_metrics_dict defines them.
+        Exactly one of
+          id_lists [n, m]  ids of the OTHER side (items for user_side=True), m <= 256, from
+                           anywhere; an id the model does not know is an open slot, as in
+                           list_similarity
+          top              the lists are made here: recommend_all(top) with the same
+                           exclude / candidates
+        candidates also defines the catalogue the coverage group is measured over.
+        Popularity is the other side's rating counts (popularity()), the listing side's row
+        count standing for the number of raters; a core built from_factors has no ratings and
+        takes popularity=(ids, counts) — without it the three popularity fields are NaN and
+        the rest is returned all the same.  The long tail is every catalogue row outside the
+        floor(head_fraction * catalogue rows) most-rated ones (ties by ascending dense row).
+        per_row: also "per_row" (f64 [n, 3] on the device: novelty, mean popularity, long-tail
+        share of each list, NaN where undefined) and, with top=, "keys" (the ids of the
+        rows)."""
+        if (id_lists is None) == (top is None):
+            raise ValueError("list_metrics takes either id_lists or top=, not both and not "
+                             "neither")
+        head_fraction = float(head_fraction)
+        if not 0.0 < head_fraction < 1.0:
+            raise ValueError(f"head_fraction must be inside (0, 1), got {head_fraction}")
+        if top is not None and not 1 <= int(top) <= LIST_MAX_AT:
+            raise ValueError(f"top must be in [1, {LIST_MAX_AT}], got {top}")
+        if id_lists is not None:
+            shape = tuple(id_lists.shape) if hasattr(id_lists, "shape") else np.shape(id_lists)
+            if len(shape) != 2 or not 1 <= int(shape[1]) <= LIST_MAX_AT:
+                raise ValueError(f"id_lists must be [n, m] with 1 <= m <= {LIST_MAX_AT}, got "
+                                 f"shape {shape}")
+            if exclude is not None:
+                raise ValueError("exclude= shapes the lists made with top=; lists given as "
+                                 "id_lists are taken as they are")
+        if self.U is None or self.V is None:
+            raise ValueError("list_metrics needs factors: fit() the core or build it "
+                             "from_factors")
+        qi, Q, oi, _ = self._sides(user_side)
+        keys = None
+        if id_lists is not None:
+            rows = oi.rows_of(_to_device(id_lists, torch.int32, self.device)).to(torch.int32)
+        else:
+            at = min(int(top), oi.n)
+            idx, _ = self._topk(Q, qi.n, user_side, at, exclude, candidates)
+            rows, keys = idx[:, :at], qi.ids()
+        out = self._list_metrics_of_rows(rows, user_side, candidates=candidates,
+                                        popularity=popularity, head_fraction=head_fraction,
+                                        per_row=per_row)
+        if per_row and keys is not None:
+            out["keys"] = keys
+        return out
+
+    def _list_metrics_of_rows(self, rows: torch.Tensor, user_side: bool = True, *,
+                             candidates=None, popularity=None, head_fraction: float = 0.2,
+                             per_row: bool = False) -> dict:
+        """list_metrics for lists that hold DENSE rows of the other side already (int32
+        [n, m] on the device, -1 = open slot): the catalogue from `candidates`, popularity
+        from the rating blocks or from popularity=(ids, counts), then the three K15 calls."""
+        qi, _, oi, _ = self._sides(user_side)
+        dev = self.device
+        bits = cat_rows = None
+        if candidates is not None:
+            c = _to_device(candidates, torch.int32, dev)
+            cat_rows = torch.unique(oi.rows_of(c))
+            cat_rows = cat_rows[cat_rows >= 0]
+            bits = _filters.pack_allow_bits(cat_rows, oi.n)
+        pop = self.popularity(user_side)
+        if popularity is not None:
+            ids, cnt = popularity
+            r = oi.rows_of(_to_device(ids, torch.int32, dev))
+            cnt = _to_device(cnt, torch.int32, dev).reshape(-1)
+            if r.numel() != cnt.numel():
+                raise ValueError("popularity: ids and counts must have the same length")
+            pop = torch.zeros(oi.n, dtype=torch.int32, device=dev)
+            pop[r[r >= 0]] = cnt[r >= 0]
+        out, pr = list_metrics_rows(rows, int(rows.shape[1]), oi.n, self.ws, allow_bits=bits,
+                                    cat_rows=cat_rows, pop=pop, n_pop=qi.n,
+                                    head_fraction=head_fraction, per_row=per_row)
+        if per_row:
+            out["per_row"] = pr
+        return out
 
     # ---- K7: rows the model has never seen ----
     def _fold_in(self, ids, other_ids, ratings, reg, implicit, alpha, user_side,

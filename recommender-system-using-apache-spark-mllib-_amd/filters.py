@@ -20,7 +20,8 @@ import torch
 __all__ = ["pack_allow_bits", "exclusion_lists", "relevance_lists", "ragged_rows",
            "relevance_lists_weighted", "reject_sharded_filters", "reject_sharded_fold_in",
            "reject_sharded_regression", "reject_sharded_full_rank", "reject_sharded_explain",
-           "reject_sharded_similar", "reject_sharded_nonnegative", "reject_sharded_diversify"]
+           "reject_sharded_similar", "reject_sharded_nonnegative", "reject_sharded_diversify",
+           "reject_sharded_list_metrics"]
 
 
 def pack_allow_bits(rows: torch.Tensor, n_v: int) -> torch.Tensor:
@@ -166,6 +167,15 @@ def reject_sharded_diversify(sharded_engine: bool = False) -> None:
         "recommend_diverse / list_similarity are not supported by the sharded engine "
         "(ShardedALS) yet: diversify lists on a single-GPU ALSCore (e.g. ALSCore.from_factors "
         "over the gathered factors)")
+
+
+def reject_sharded_list_metrics() -> None:
+    """The sharded engine carries list_metrics with the single-GPU signature and refuses it,
+    as it refuses list_similarity."""
+    raise NotImplementedError(
+        "list_metrics is not supported by the sharded engine (ShardedALS) yet: measure the "
+        "lists on a single-GPU ALSCore (e.g. ALSCore.from_factors over the gathered factors, "
+        "with popularity=)")
 
 
 def reject_sharded_regression() -> None:

@@ -687,3 +687,77 @@ class ALSModel:
         ils = _engine.list_similarity_rows(rows, Vo, oi.n, self._core.rank)
         return pd.DataFrame({key_col: np.asarray(recommendations[key_col]),
                              "intraListSimilarity": ils.cpu().numpy()})
+
+    # -- the lists of all users together (K15): coverage, concentration, popularity --
+    def _padded_rows(self, recommendations):
+        """(user_side, key column, dense rows int32 [n, m] on the device, -1 = open slot) of
+        lists in the shape recommendForAllUsers / recommendForAllItems return."""
+        p = self._p
+        user_side = p["userCol"] in recommendations
+        key_col = p["userCol"] if user_side else p["itemCol"]
+        if key_col not in recommendations:
+            raise ValueError(f"recommendations must have a {p['userCol']!r} or {p['itemCol']!r} "
+                             "column")
+        lists = [[int(a) for a, _ in recs] for recs in recommendations["recommendations"]]
+        m = max([len(x) for x in lists] + [1])
+        _, _, oi, _ = self._core._sides(user_side)
+        ids = np.zeros((len(lists), m), np.int64)
+        known = np.zeros((len(lists), m), bool)
+        for r, x in enumerate(lists):
+            ids[r, :len(x)] = x
+            known[r, :len(x)] = True
+        dev = self._core.device
+        rows = oi.rows_of(torch.as_tensor(ids, device=dev))
+        rows = torch.where(torch.as_tensor(known, device=dev), rows, -1).to(torch.int32)
+        return user_side, key_col, rows
+
+    def _list_quality(self, recommendations, numItems, exclude, candidates, headFraction,
+                      popularity, per_row):
+        if (recommendations is None) == (numItems is None):
+            raise ValueError("pass either recommendations or numItems=, not both and not neither")
+        if popularity is not None:
+            ids, cnt = popularity
+            popularity = (check_integers(np.asarray(ids).reshape(-1), "popularity ids"),
+                          check_integers(np.asarray(cnt).reshape(-1), "popularity counts"))
+        kw = dict(popularity=popularity, head_fraction=float(headFraction), per_row=per_row)
+        if numItems is not None:
+            out = self._core.list_metrics(top=int(numItems), user_side=True,
+                                          **self._filters(exclude, candidates, True), **kw)
+            return out, self._p["userCol"], out.get("keys")
+        if exclude is not None:
+            raise ValueError("exclude= shapes the lists made with numItems=; given "
+                             "recommendations are taken as they are")
+        user_side, key_col, rows = self._padded_rows(recommendations)
+        out = self._core._list_metrics_of_rows(
+            rows, user_side, candidates=self._filters(None, candidates, user_side)["candidates"],
+            **kw)
+        return out, key_col, np.asarray(recommendations[key_col])
+
+    def evaluateListQuality(self, recommendations=None, *, numItems=None, exclude=None,
+                            candidates=None, headFraction: float = 0.2, popularity=None) -> dict:
+        """Do all users get the same few blockbusters?  The lists of everybody looked at
+        together (K15): {"coverage" (share of the catalogue listed at least once), "gini" and
+        "entropy" of item exposure, "effectiveItems" (2 ** entropy), "personalization" (1 - the
+        mean overlap of two users' lists), "topItemShare", "novelty" (mean self-information,
+        bits), "averagePopularity", "longTailShare", "lists", "entries", "skipped"}.
+        recommendations: a DataFrame as recommendForAllUsers / recommendForAllUsersDiverse
+        return (lists of at most 256 entries; the key column decides the side, as in
+        intraListSimilarity); or numItems=: the lists are made here, with exclude / candidates
+        as recommendForAllUsers.  candidates also defines the catalogue.  headFraction: the
+        most-rated share of the catalogue that is NOT the long tail.  Popularity is how often
+        each item was rated in the data the model was fitted on; a loaded model has none and
+        takes popularity=(item ids, counts) — without it the three popularity fields are NaN."""
+        return self._list_quality(recommendations, numItems, exclude, candidates, headFraction,
+                                  popularity, False)[0]
+
+    def listQualityPerRow(self, recommendations=None, *, numItems=None, exclude=None,
+                          candidates=None, headFraction: float = 0.2, popularity=None):
+        """evaluateListQuality's popularity measures list by list: DataFrame[key column,
+        novelty, averagePopularity, longTailShare], NaN where a list has nothing to measure."""
+        import pandas as pd
+        out, key_col, keys = self._list_quality(recommendations, numItems, exclude, candidates,
+                                                headFraction, popularity, True)
+        pr = out["per_row"].cpu().numpy()
+        keys = keys.cpu().numpy() if isinstance(keys, torch.Tensor) else keys
+        return pd.DataFrame({key_col: keys, "novelty": pr[:, 0], "averagePopularity": pr[:, 1],
+                             "longTailShare": pr[:, 2]})

@@ -24,6 +24,12 @@ upstream's definitions (mllib/evaluation/RegressionMetrics.scala): one pass of k
 (als_regression_moments_cols) over the two fp64 columns.  For a fitted model use
 ``MatrixFactorizationModel.regressionMetrics`` / ``ALSModel.evaluateRegression``, which
 form the predictions inside the same pass.
+
+``ListMetrics(lists)`` has no Spark counterpart: the beyond-accuracy measures of a set of
+recommendation lists taken together (catalogue coverage, Gini index and entropy of item
+exposure, personalisation, novelty, average popularity, long-tail share), for lists from
+anywhere; kernels K15.  For a fitted model use ``MatrixFactorizationModel.listMetrics`` /
+``ALSModel.evaluateListQuality``.
 """
 from __future__ import annotations
 
@@ -35,7 +41,7 @@ from .. import engine as _engine
 from .. import filters as _filters
 from .._data import check_integers
 
-__all__ = ["RankingMetrics", "RegressionMetrics"]
+__all__ = ["RankingMetrics", "RegressionMetrics", "ListMetrics"]
 
 
 def _id_array(x, what: str) -> np.ndarray:
@@ -168,3 +174,75 @@ class RegressionMetrics:
     @property
     def r2(self) -> float:
         return self._m["r2"]
+
+
+class ListMetrics:
+    """What a set of recommendation lists looks like as a whole (K15).
+
+    lists: an iterable of id sequences, one per user, at most 256 ids each (shorter lists are
+    padded with open slots).  popularity: {id: count} or (ids, counts), how often each item
+    was rated; without it novelty, averagePopularity and longTailShare are NaN.  numUsers: the
+    number of raters the counts come from (None: the number of lists).  catalog: the ids
+    exposure is measured over (None: every id named by popularity or by a list, taken together;
+    with a catalog, a listed id outside it is skipped).  The long tail is what lies outside the
+    most-rated fifth of the catalogue.  The ids are mapped to dense rows on the host, the three
+    measures run on the device (als_list_exposure, als_list_concentration,
+    als_list_novelty).  Each field of engine.LIST_METRIC_FIELDS is an attribute; toDict()
+    returns them all."""
+
+    def __init__(self, lists, popularity=None, numUsers=None, catalog=None):
+        lists = [_id_array(x, "list") for x in lists]
+        width = max([len(x) for x in lists] + [1])
+        if width > _engine.LIST_MAX_AT:
+            raise ValueError(f"lists of {width} entries > {_engine.LIST_MAX_AT} are not "
+                             "supported by the list-metrics kernels")
+        if numUsers is not None and int(numUsers) < 1:
+            raise ValueError(f"numUsers must be >= 1, got {numUsers}")
+        pop_ids = pop_cnt = None
+        if popularity is not None:
+            if isinstance(popularity, dict):
+                pop_ids, pop_cnt = list(popularity.keys()), list(popularity.values())
+            else:
+                pop_ids, pop_cnt = popularity
+            pop_ids = _id_array(pop_ids, "popularity id")
+            pop_cnt = _id_array(pop_cnt, "popularity count")
+            if len(pop_ids) != len(pop_cnt):
+                raise ValueError("popularity: ids and counts must have the same length")
+        flat = np.concatenate(lists) if lists else np.zeros(0, np.int32)
+        if catalog is not None:
+            cat = np.unique(_id_array(catalog, "catalog"))
+        elif pop_ids is not None:
+            cat = np.unique(np.concatenate([pop_ids, flat]))
+        else:
+            cat = np.unique(flat)
+        n_v = len(cat)
+
+        def dense(ids):
+            if n_v == 0:
+                return np.full(len(ids), -1, np.int64)
+            pos = np.minimum(np.searchsorted(cat, ids), n_v - 1)
+            return np.where(cat[pos] == ids, pos, -1)
+
+        idx = np.full((len(lists), width), -1, np.int32)
+        for r, x in enumerate(lists):
+            idx[r, :len(x)] = dense(x)
+        _lib.require_gpu()
+        dev = torch.device("cuda", torch.cuda.current_device())
+        pop = None
+        if pop_ids is not None:
+            host = np.zeros(n_v, np.int32)
+            d = dense(pop_ids)
+            host[d[d >= 0]] = pop_cnt[d >= 0]
+            pop = torch.as_tensor(host, device=dev)
+        n_pop = int(numUsers) if numUsers is not None else max(len(lists), 1)
+        self._m, _ = _engine.list_metrics_rows(
+            torch.as_tensor(idx, device=dev), width, n_v, _engine.Workspace(dev), pop=pop,
+            n_pop=n_pop)
+
+    def toDict(self) -> dict:
+        return dict(self._m)
+
+    def __getattr__(self, name):
+        if name in _engine.LIST_METRIC_FIELDS:
+            return self._m[name]
+        raise AttributeError(name)

@@ -247,6 +247,18 @@ class MatrixFactorizationModel:
                           if np.isfinite(s)], float(v))
                 for k, ri, rs, v in zip(keys, ids, sc, ils)]
 
+    def listMetrics(self, num: int, *, exclude=None, candidates=None) -> dict:
+        """Every user's top-`num` products looked at together (K15): {"coverage", "gini",
+        "entropy", "effectiveItems", "personalization", "topItemShare", "novelty",
+        "averagePopularity", "longTailShare", "lists", "entries", "skipped"} — how much of the
+        catalogue the lists reach, how concentrated exposure is, how obscure the listed
+        products are and how much two users' lists overlap (engine.list_metrics_dict).
+        exclude / candidates as recommendProductsForUsers; candidates also defines the
+        catalogue.  Lists and measures stay on the device.  A loaded model holds no rating
+        counts: its three popularity fields are NaN."""
+        return self._core.list_metrics(top=int(num), user_side=True,
+                                       **self._filters(exclude, candidates, True))
+
     def foldInUsers(self, ratings, lambda_: float, *, implicit: bool = False,
                     alpha: float = 0.01, nonnegative: bool = False):
         """Factors for users that are not in the model, from their (user, product,
