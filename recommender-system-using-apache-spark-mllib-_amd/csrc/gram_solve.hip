@@ -1455,8 +1455,29 @@ __device__ __forceinline__ float sel_mask(float v, float w) {
 // the pivot's row updates, so each ds_bpermute has a whole pivot to land; one DPP fmac
 // more per pivot, still bit-identical): W1 user rows 94.9 -> 93.0 ms, 273.4 -> 271.0
 // ms/iter at 4096-rating tasks (profiles/r06/ab_lookahead2.jsonl).
-template <bool LA = false, class Hook>
+//
+// LEAN (the full-rank 33-64 explicit launch, where the VALU is the busiest unit): two
+// VALU instructions fewer per pivot, every entry's operations as before.  The pivot's
+// own-lane copy comes from the broadcast row (lane p of it IS the pivot, the same bits
+// as its row_newbcast copy d), so d feeds the reciprocal alone and rides in its DPP
+// operand; and row p's write (f off the pivot, -1 on it, row group p/4 only) is one
+// v_cndmask_b32_dpp whose row_mask keeps the other row groups' register.
+template <int P>
+__device__ __forceinline__ void put_pivot_row(float& b, float f, float neg1) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  // the VOP2 DPP select takes its lane mask from vcc (a scalar move, no VALU)
+  const uint64_t msk = 0x0001000100010001ull << P;
+  asm volatile("s_mov_b64 vcc, %3\n\t"
+               "v_cndmask_b32_dpp %0, %1, %2, vcc quad_perm:[0,1,2,3] row_mask:%4 bank_mask:0xf"
+               : "+v"(b)
+               : "v"(f), "v"(neg1), "s"(msk), "i"(1 << (P >> 2))
+               : "vcc");
+#endif
+}
+
+template <bool LA = false, bool LEAN = false, class Hook>
 __device__ __forceinline__ float sweep16c(floatx4& Bv, Hook&& hook, float& dself_out) {
+  static_assert(!(LA && LEAN), "the lean form keeps the pivot row's broadcast, not its look-ahead copy");
   // Bv was just written by the matrix cores (the pivot block's Schur update) and is
   // read below by inline DPP asm, which the hazard recognizer does not see: the XDL
   // write -> VALU read wait states by hand (tests/test_isa_hazards.py checks the rest)
@@ -1475,11 +1496,13 @@ __device__ __forceinline__ float sweep16c(floatx4& Bv, Hook&& hook, float& dself
   float rd = rcp_t(d);
   float f = rowp * rd;
   float nf = sel_lane16_n<0>(0.f, f);
+  float rowc = rowp;  // LEAN: the current pivot's broadcast row
+  const float neg1 = -1.f;
   static_for<16>([&](auto pc) {
     constexpr int p = decltype(pc)::value;
     constexpr int qp = p >> 2, rp = p & 3, rn = (p + 1) & 3;
     asm volatile("s_nop 1" ::: "memory");
-    float dn = 0.f, rdn = 0.f, fn = 0.f, nfn = 0.f;
+    float dn = 0.f, rdn = 0.f, fn = 0.f, nfn = 0.f, rowcn = 0.f;
     if constexpr (LA) {
       if constexpr (p + 1 < 16) {  // row p+1 after pivot p, on its broadcast copy
         fmac_bcast16<p>(pre, nf);
@@ -1510,6 +1533,7 @@ __device__ __forceinline__ float sweep16c(floatx4& Bv, Hook&& hook, float& dself
         rdn = rcp_t(dn);
         fn = rown * rdn;
         nfn = sel_lane16_n<p + 1>(0.f, fn);
+        rowcn = rown;
       }
       static_for<4>([&](auto rc) {
         constexpr int r = decltype(rc)::value;
@@ -1517,10 +1541,15 @@ __device__ __forceinline__ float sweep16c(floatx4& Bv, Hook&& hook, float& dself
       });
     }
     // row p (row group qp): f off the pivot, -1 on it (scaled by 1/d at the end)
-    B[rp] = sel_mask<0xFFFFull << (16 * qp)>(sel_lane16<p>(-1.f, f), B[rp]);
-    dself = sel_lane16<p>(d, dself);
+    if constexpr (LEAN) {
+      put_pivot_row<p>(B[rp], f, neg1);
+      dself = sel_lane16<p>(rowc, dself);
+    } else {
+      B[rp] = sel_mask<0xFFFFull << (16 * qp)>(sel_lane16<p>(-1.f, f), B[rp]);
+      dself = sel_lane16<p>(d, dself);
+    }
     hook(pc);
-    d = dn; rd = rdn; f = fn; nf = nfn;
+    d = dn; rd = rdn; f = fn; nf = nfn; rowc = rowcn;
   });
   const float s = rcp_t(dself);
 #pragma unroll
@@ -1731,7 +1760,9 @@ __device__ __forceinline__ half8v dup_lo(const half8v& v) {
 // 2 / 4 (the n x n dual systems of short rows, gram_solve_dual_kernel).  Returns
 // whether every pivot was positive and the solution finite; xcol[c] on lane (q, m)
 // = solution entry of variable (block c, index m), every row group q.
-template <int NB, bool SPLIT = kW1SplitSchur<NB>>
+// FULL: k == 16 NB is known at compile time (no padded dims: every test of a dim against k
+// folds away) and the diagonal blocks take the lean sweep.
+template <int NB, bool SPLIT = kW1SplitSchur<NB>, bool FULL = false>
 __device__ __forceinline__ bool w1_solve_x(floatx4 (&A)[NB * (NB + 1) / 2], float (&bcol)[NB],
                                            float* __restrict__ lds, int k, float (&xcol)[NB],
                                            float cond_max = kCondMax) {
@@ -1782,8 +1813,8 @@ __device__ __forceinline__ bool w1_solve_x(floatx4 (&A)[NB * (NB + 1) / 2], floa
       // swept in the C layout: Gm comes out where the MFMAs read it
       Gm = A[w1_tile<NB>(K, K)];
       float ds;
-      dmin = fminf(dmin, sweep16c<NB == 8>(Gm, hook, ds));
-      track_pivot(ds, m * NB + K < k);
+      dmin = fminf(dmin, sweep16c<NB == 8, FULL>(Gm, hook, ds));
+      track_pivot(ds, FULL || m * NB + K < k);
       const float bK = K == 0 ? bcol[0] : reduce_rows4(bcol[K]);  // partials -> b_K[m]
       if (q == 0) vec[m] = bK;
       wave_lds_order();
@@ -1940,19 +1971,20 @@ __device__ __forceinline__ bool w1_solve_x(floatx4 (&A)[NB * (NB + 1) / 2], floa
 
 // w1_solve_x, then the solution row written un-permuted: dim d = i * NB + c <->
 // block c, index i = lane m; dims in [k, ld) written as zero.
-template <int NB, bool SPLIT = kW1SplitSchur<NB>>
+template <int NB, bool SPLIT = kW1SplitSchur<NB>, bool FULL = false>
 __device__ __forceinline__ bool w1_solve(floatx4 (&A)[NB * (NB + 1) / 2], float (&bcol)[NB],
                                          float* __restrict__ lds, int k,
                                          float* __restrict__ xrow, int ld,
                                          float cond_max = kCondMax) {
   float xcol[NB];
-  const bool ok = w1_solve_x<NB, SPLIT>(A, bcol, lds, k, xcol, cond_max);
+  const bool ok = w1_solve_x<NB, SPLIT, FULL>(A, bcol, lds, k, xcol, cond_max);
   const int lane = threadIdx.x & 63, m = lane & 15;
   if (lane < 16) {
 #pragma unroll
     for (int c = 0; c < NB; ++c) {
       const int d = m * NB + c;
-      if (d < ld) xrow[d] = (d < k && ok) ? xcol[c] : 0.f;
+      if constexpr (FULL) xrow[d] = ok ? xcol[c] : 0.f;  // d < k = 16 NB <= ld
+      else if (d < ld) xrow[d] = (d < k && ok) ? xcol[c] : 0.f;
     }
   }
   // a caller's ld may exceed k_pad = 16 NB (any ld >= k is allowed): those columns too
@@ -2269,7 +2301,7 @@ __device__ __forceinline__ void zero_acc(AccT (&tot)[N][4], AccT (&bt)[NRA]) {
 // scal[1] = max |rating| (prep phase).  Explicit: Gram and rhs from the split
 // table Ysp (kp words per row, zero row `zero_row`); implicit: from Y, split in
 // registers after the per-rating confidence weight.
-template <bool ADD_YTY, int NB = kW1NB, bool SPLIT = kW1SplitSchur<NB>>
+template <bool ADD_YTY, int NB = kW1NB, bool SPLIT = kW1SplitSchur<NB>, bool FULL = false>
 __device__ __forceinline__ void w1_finish_and_solve(floatx4 (&A)[NB * (NB + 1) / 2],
                                                     float scale, float (&bt)[NB], int64_t n_reg,
                                                     const float* __restrict__ ytyC,
@@ -2283,18 +2315,32 @@ __device__ __forceinline__ void w1_finish_and_solve(floatx4 (&A)[NB * (NB + 1) /
 // 2.25 ms/iter; round 5, after the lean sweep, 11 spills: 2.14 vs 2.02 ms/iter,
 // profiles/r05/ab_occupancy.jsonl, both at the panel's 12,288 B of LDS, i.e. still
 // three waves.  Rank 33-64 now fits four without spills: profiles/r09/occupancy4.md.)
-template <int CN, bool IMPLICIT>
-__global__ __launch_bounds__(64, (kFusedWaves<CN, IMPLICIT>)) void gram_solve_kernel(
+//
+// CNP = CN, the rank's 16-dim blocks — or -4 for explicit ranks 33-63.  The explicit
+// CN = 4 instantiation proper, gram_solve_kernel<4, false>, is FULL: the host launches it
+// at rank 64 only, where k = k_pad = 16 CN is known at compile time.  The user launch of
+// the rank-64 iteration is bound by VALU issue (profiles/r09/occupancy4.md section 4), and a
+// good part of a light row's VALU instructions outside the Gram loop only masked padded
+// dims that a full rank does not have, or copied tiles around the k == k_pad branch; with
+// FULL they are not compiled, and the diagonal blocks take the lean sweep
+// (profiles/r10/valu_trim.md).  Ranks 33-63 keep the run-time masks: <-4, false>.
+constexpr int kCnPadded64 = -4;
+template <int CNP, bool IMPLICIT>
+__global__ __launch_bounds__(64, (kFusedWaves<(CNP < 0 ? -CNP : CNP), IMPLICIT>)) void gram_solve_kernel(
     const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
     const float* __restrict__ val, const int32_t* __restrict__ light_rows,
     const int32_t* __restrict__ chunk_row, const int64_t* __restrict__ chunk_begin,
     const int64_t* __restrict__ chunk_end, int32_t n_chunks, int32_t n_light,
-    const float* __restrict__ Y, float* __restrict__ X, int ld, int k, float reg, float alpha,
+    const float* __restrict__ Y, float* __restrict__ X, int ld, int k_arg, float reg, float alpha,
     const double* __restrict__ yty, float* __restrict__ slots, int32_t* __restrict__ status,
     const float* __restrict__ scal, const uint32_t* __restrict__ Ysp, int32_t kp,
     int32_t zero_row, RescueList rl) {
-  constexpr int NT = Cfg<CN>::NT;
+  constexpr int CN = CNP < 0 ? -CNP : CNP;
+  constexpr bool FULL = !IMPLICIT && CNP == 4;
+  static_assert(CNP > 0 || (CNP == kCnPadded64 && !IMPLICIT), "-4: explicit ranks 33-63 only");
   __shared__ __attribute__((aligned(16))) unsigned char smem[FusedSmemBytes<CN, IMPLICIT>::value];
+  constexpr int NT = Cfg<CN>::NT;
+  const int k = FULL ? 16 * CN : k_arg;
   floatx4 acc[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) acc[t] = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -2361,8 +2407,8 @@ __global__ __launch_bounds__(64, (kFusedWaves<CN, IMPLICIT>)) void gram_solve_ke
     // inverses + fp32 MFMA), in the Gram's scale
     static_assert((int)sizeof(float) * W1LdsT<4>::SIZE <= FusedSmemBytes<4, false>::value,
                   "W1<4> LDS");
-    w1_finish_and_solve<false, 4, false>(acc, inv2, bt, n_reg, nullptr, smem, k, reg,
-                                  X + (int64_t)row * ld, ld, row, rl);
+    w1_finish_and_solve<false, 4, false, FULL>(acc, inv2, bt, n_reg, nullptr, smem, k, reg,
+                                               X + (int64_t)row * ld, ld, row, rl);
   } else {
     finish_and_solve<CN, IMPLICIT, float>(tot, bt, n_reg, smem, k, reg, yty,
                                           X + (int64_t)row * ld, ld, row, rl,
@@ -2575,7 +2621,7 @@ __global__ __launch_bounds__(64) void yty_ctab_kernel(const double* __restrict__
 // in that scale: (A + (lambda n / scale) I) x = b / scale  (+ YtY / scale for
 // implicit, from the C-layout table).  Padded dims (k < 128) become identity
 // rows/columns.  bt: per-lane rhs partials (summed over the 4 rating slots here).
-template <bool ADD_YTY, int NB, bool SPLIT>
+template <bool ADD_YTY, int NB, bool SPLIT, bool FULL>
 __device__ __forceinline__ void w1_finish_and_solve(floatx4 (&A)[NB * (NB + 1) / 2],
                                                     float scale, float (&bt)[NB], int64_t n_reg,
                                                     const float* __restrict__ ytyC,
@@ -2584,12 +2630,13 @@ __device__ __forceinline__ void w1_finish_and_solve(floatx4 (&A)[NB * (NB + 1) /
                                                     RescueList rl, float cond_max) {
   constexpr int NT_ = NB * (NB + 1) / 2;
   const int lane = threadIdx.x & 63, q = lane >> 4, m = lane & 15;
-  const float inv = 1.f / scale;  // power of two: exact
+  // power of two: exact (FULL: from the exponent, not an IEEE division's dozen VALU)
+  const float inv = FULL ? ldexpf(1.f, 1 - __builtin_amdgcn_frexp_expf(scale)) : 1.f / scale;
   float bq[NB];
 #pragma unroll
   for (int c = 0; c < NB; ++c) {
     const float v = reduce_rows4(bt[c]) * inv;
-    bq[c] = m * NB + c < k ? v : 0.f;
+    bq[c] = (FULL || m * NB + c < k) ? v : 0.f;
   }
   const float lam = (float)((double)reg * (double)n_reg) * inv;
   if constexpr (ADD_YTY) {
@@ -2599,7 +2646,7 @@ __device__ __forceinline__ void w1_finish_and_solve(floatx4 (&A)[NB * (NB + 1) /
       for (int r = 0; r < 4; ++r) A[t][r] = fmaf(ytyC[(t * 4 + r) * 64 + lane], inv, A[t][r]);
     });
   }
-  if (k == NB * 16) {  // uniform: no padded dims, lambda on the diagonal only
+  if (FULL || k == NB * 16) {  // uniform: no padded dims, lambda on the diagonal only
     static_for<NB>([&](auto cc) {
       constexpr int c = decltype(cc)::value;
       constexpr int t = w1_tile<NB>(c, c);
@@ -2621,7 +2668,8 @@ __device__ __forceinline__ void w1_finish_and_solve(floatx4 (&A)[NB * (NB + 1) /
       }
     });
   }
-  const bool ok = w1_solve<NB, SPLIT>(A, bq, reinterpret_cast<float*>(smem), k, xrow, ld, cond_max);
+  const bool ok =
+      w1_solve<NB, SPLIT, FULL>(A, bq, reinterpret_cast<float*>(smem), k, xrow, ld, cond_max);
   if (!ok) rescue_append(rl, row);  // re-solved in fp64
 }
 
@@ -3503,15 +3551,16 @@ int als_solve_half(const int64_t* row_ptr, const int32_t* col, const float* val,
 #define ALS_SOLVE_LAUNCH(CN, IMP)                                                                 \
   do {                                                                                            \
     float* slots_f = reinterpret_cast<float*>(slots);                                             \
+    /* explicit rank 33-64: gram_solve_kernel<4, false> is compiled for k == k_pad */             \
+    auto* launch1 = (CN == 4 && !IMP && k != kp) ? gram_solve_kernel<(IMP ? CN : kCnPadded64), IMP> \
+                                                 : gram_solve_kernel<CN, IMP>;                    \
     if (g1)                                                                                       \
-      gram_solve_kernel<CN, IMP><<<g1, 64, 0, st>>>(row_ptr, col, val, light_rows, chunk_row,     \
-                                                    chunk_begin, chunk_end, n_chunks,             \
-                                                    n_light_primal, Y_src, X_dst, ld, k, reg,     \
-                                                    alpha, yty_packed,                            \
-                                                    slots_f + (size_t)chunk_slot0 * Cfg<CN>::SLOT, \
-                                                    status_dev, scal,                             \
-                                                    Ysp, kp, zero_row, rl);  \
-    ALS_LAUNCH_CHECK();                                                                           \
+      launch1<<<g1, 64, 0, st>>>(row_ptr, col, val, light_rows, chunk_row, chunk_begin,           \
+                                 chunk_end, n_chunks, n_light_primal, Y_src, X_dst, ld, k, reg,   \
+                                 alpha, yty_packed,                                               \
+                                 slots_f + (size_t)chunk_slot0 * Cfg<CN>::SLOT, status_dev, scal, \
+                                 Ysp, kp, zero_row, rl);                                          \
+    ALS_LAUNCH_CHECK();                                                                         \
     if (gd && CN == 4 && !IMP) {                                                                  \
       gram_solve_dual_kernel<64><<<gd, 64, 0, st>>>(row_ptr, col, val,                            \
                                                     light_rows + n_light_primal, X_dst, ld, reg,  \
