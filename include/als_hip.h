@@ -729,6 +729,67 @@ int als_list_novelty(const int32_t* idx, int64_t n_q, int32_t idx_ld, int32_t at
                      const uint32_t* tail_bits, double* sums_out, double* per_row_out,
                      void* ws, size_t ws_bytes, void* stream);
 
+/* ---- K16: rating statistics and bias baselines.  Replaces the reference's
+ *      getCountsAndAverages and "more than 500 reviews" filter (RecommenderSystem.py:49-86)
+ *      and its training-mean baseline (RecommenderSystem.py:172-177); with a bias table it is
+ *      the sweep of the damped baseline predictor mu + b_u + b_i (Koren 2010, section 2.1).
+ *      Spark has neither -------------------------------------------------------------------- */
+
+/* Added under ABI 9 without a version bump: six new symbols only, nothing existing changes.
+ * A by-value double does not appear in this header; the three fp64 scalars below are passed
+ * by address, *_host pointing to HOST memory that is read before the call returns (NULL = 0).
+ *
+ * als_row_moments: one CSR side as a RatingBlock holds it (row_ptr int64 [n_rows + 1], col
+ * int32 [nnz], val fp32 [nnz]).  Over the terms
+ *   e_j = (double)val_j - *offset_host - (other ? other[col_j] : 0)
+ * of each row, `other` NULL or fp64 [n_cols] (a col_j outside [0, n_cols) takes 0 and is not
+ * dereferenced; with other == NULL col is never read and may be NULL):
+ *   moments  fp64 [n_rows, 5] = { n, sum e, M2 = sum (e - mean_row)^2, min e, max e }; n is
+ *            exact, min and max are exact and NaN for a row without ratings (whose n, sum and
+ *            M2 are 0)
+ *   total    fp64 [5] = the same five over all ratings of the side (NaN min / max when
+ *            nnz = 0); sum e^2 = M2 + sum^2 / n is a baseline's training SSE
+ * All accumulation is fp64.  M2 is merged by Chan's rule (never sum e^2 - sum^2 / n).  No
+ * atomics: the order of every addition is a function of row_ptr alone, so two calls give
+ * identical bytes.  A row of more than als_rating_stats_task() ratings is cut into tasks of
+ * that many, one workgroup each, merged in ascending task order; every other row is read by
+ * a 16-lane group, als_rating_stats_group_rows() rows per workgroup.  col and val are read
+ * with 16-byte loads when both are 16-byte aligned and with 4-byte loads otherwise, to the
+ * same bits.  Row bounds are clamped to [0, nnz], so a row_ptr that does not describe nnz
+ * ratings gives wrong numbers and no access outside col / val.
+ * Scratch: als_rating_stats_scratch_bytes(nnz, n_rows) bytes, 16-byte aligned (0 for sizes
+ * the call rejects); moments, total and other 8-byte aligned.
+ *
+ * als_bias_update: bias_out[row] (fp64 [n_rows]) = sum_row / (*damping_host + n_row) from a
+ * moments table, 0 for a row with n = 0.  A separate call, not an output of the sweep: the
+ * sweep stays a statistics pass and the update is one thread per row.
+ *
+ * als_baseline_predict: n pairs of dense rows (int32, -1 or anything outside [0, n_users) /
+ * [0, n_items) = unknown id):
+ *   pred[e]  (fp32) = *mu_host + (user known ? bu[urow] : 0) + (item known ? bi[irow] : 0),
+ *            summed in fp64 and rounded once; bu / bi fp64, each may be NULL = all zero
+ *   known[e] (uint8) = bit 0 user known, bit 1 item known
+ *
+ * Checked on the host before any device call: a negative size is ALS_EINVAL; nnz >= 2^40,
+ * n_rows >= 2^31 - 1 or n >= 2^39 ALS_EUNSUPPORTED; a NULL row_ptr / moments / total /
+ * bias_out / urow / irow / pred / known, a NULL val (or col, with other) when nnz > 0, a
+ * misaligned table or scratch and a negative or non-finite damping ALS_EINVAL; a short
+ * scratch ALS_EWORKSPACE.  n_rows == 0 and n == 0 are valid and do nothing (total is then
+ * left as it is).  Costs beside torch and beside the byte floor: DESIGN.md section K16. */
+int32_t als_rating_stats_task(void);
+int32_t als_rating_stats_group_rows(void);
+size_t als_rating_stats_scratch_bytes(int64_t nnz, int64_t n_rows);
+int als_row_moments(const int64_t* row_ptr, const int32_t* col, const float* val, int64_t nnz,
+                    int32_t n_rows, int32_t n_cols, const double* other,
+                    const double* offset_host, double* moments, double* total, void* ws,
+                    size_t ws_bytes, void* stream);
+int als_bias_update(const double* moments, int32_t n_rows, const double* damping_host,
+                    double* bias_out, void* stream);
+int als_baseline_predict(const int32_t* urow, const int32_t* irow, int64_t n,
+                         const double* mu_host, const double* bu, int32_t n_users,
+                         const double* bi, int32_t n_items, float* pred, uint8_t* known,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

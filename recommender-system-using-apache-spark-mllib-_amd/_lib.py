@@ -108,6 +108,12 @@ SIGNATURES = {
     "als_list_concentration": (ctypes.c_int, [P, I64, P, I64, I32, P, P, SZ, P]),
     "als_list_novelty_scratch_bytes": (SZ, [I64]),
     "als_list_novelty": (ctypes.c_int, [P, I64, I32, I32, I64, P, P, I64, P, P, P, P, SZ, P]),
+    "als_rating_stats_task": (I32, []),
+    "als_rating_stats_group_rows": (I32, []),
+    "als_rating_stats_scratch_bytes": (SZ, [I64, I64]),
+    "als_row_moments": (ctypes.c_int, [P, P, P, I64, I32, I32, P, P, P, P, P, SZ, P]),
+    "als_bias_update": (ctypes.c_int, [P, I32, P, P, P]),
+    "als_baseline_predict": (ctypes.c_int, [P, P, I64, P, P, I32, P, I32, P, P, P]),
 }
 
 ABI_VERSION = 9

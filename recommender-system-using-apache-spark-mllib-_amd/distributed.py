@@ -48,7 +48,8 @@ from .filters import (reject_sharded_diversify, reject_sharded_explain, reject_s
                       reject_sharded_fold_in,
                       reject_sharded_full_rank, reject_sharded_list_metrics,
                       reject_sharded_nonnegative,
-                      reject_sharded_objective, reject_sharded_regression,
+                      reject_sharded_objective, reject_sharded_rating_stats,
+                      reject_sharded_regression,
                       reject_sharded_similar)
 
 
@@ -996,6 +997,24 @@ class ShardedALS:
                              per_row: bool = False) -> dict:
         """list_metrics for lists given as dense rows: refused like list_metrics."""
         reject_sharded_list_metrics()
+
+    def rating_stats(self, user_side: bool = False) -> dict:
+        """ALSCore.rating_stats is not offered on the sharded engine yet."""
+        reject_sharded_rating_stats()
+
+    def global_stats(self) -> dict:
+        """ALSCore.global_stats is not offered on the sharded engine yet."""
+        reject_sharded_rating_stats()
+
+    def top_rated(self, num: int, min_count: int = 0, user_side: bool = False,
+                  damping: float = 0.0):
+        """ALSCore.top_rated is not offered on the sharded engine yet."""
+        reject_sharded_rating_stats()
+
+    def fit_baseline(self, method: str = "bias", reg_user: float = 10.0, reg_item: float = 25.0,
+                     sweeps: int = 10):
+        """ALSCore.fit_baseline is not offered on the sharded engine yet."""
+        reject_sharded_rating_stats()
 
     def regression_metrics(self, users, items, ratings, through_origin: bool = False) -> dict:
         """ALSCore.regression_metrics is not offered on the sharded engine yet."""

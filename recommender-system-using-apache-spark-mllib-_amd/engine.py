@@ -16,6 +16,7 @@ Data layout in HBM (DESIGN.md "Data layout"):
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from dataclasses import dataclass
 from typing import Optional
@@ -1133,6 +1134,143 @@ def gram_dot(A: torch.Tensor, n_a: int, B: torch.Tensor, n_b: int, rank: int, ws
 
 
 # ---------------------------------------------------------------------------
+# K16: rating statistics and bias baselines
+# ---------------------------------------------------------------------------
+RATING_MOMENTS = ("n", "sum", "M2", "min", "max")   # als_row_moments' columns, and its total
+BASELINE_METHODS = ("global", "item", "user", "bias")
+
+
+def rating_stats_task() -> int:
+    """Ratings per task of a long row in K16's sweep (als_rating_stats_task)."""
+    return int(_lib.lib().als_rating_stats_task())
+
+
+def rating_stats_group_rows() -> int:
+    """Rows one workgroup of K16's sweep owns (als_rating_stats_group_rows)."""
+    return int(_lib.lib().als_rating_stats_group_rows())
+
+
+def _host_f64(x) -> ctypes.c_double:
+    """A host double the library reads through its address before the call returns."""
+    return ctypes.c_double(float(x))
+
+
+def row_moments(block_or_csr, n_cols: int, ws: Workspace, other: Optional[torch.Tensor] = None,
+                offset: float = 0.0, moments: Optional[torch.Tensor] = None,
+                total: Optional[torch.Tensor] = None):
+    """K16's sweep over one CSR side (als_row_moments): a RatingBlock, or (row_ptr int64
+    [n + 1], col int32, val fp32) device tensors.  Terms e = val - offset - other[col] (other:
+    f64 [n_cols] on the device, or None).  Returns (moments f64 [n_rows, 5], total f64 [5]),
+    columns in RATING_MOMENTS order; a row without ratings has n = sum = M2 = 0 and NaN min /
+    max.  moments / total: device tensors to write into."""
+    L = _lib.lib()
+    if isinstance(block_or_csr, RatingBlock):
+        row_ptr, col, val = block_or_csr.row_ptr, block_or_csr.col, block_or_csr.val
+    else:
+        row_ptr, col, val = block_or_csr
+    dev = row_ptr.device
+    n_rows, nnz = int(row_ptr.numel()) - 1, int(val.numel())
+    if n_rows < 0 or int(col.numel()) != nnz:
+        raise ValueError("row_moments: row_ptr needs n_rows + 1 entries and col / val one length")
+    if other is not None:
+        if other.dtype != torch.float64 or other.numel() != int(n_cols):
+            raise ValueError("row_moments: other must be a float64 table of n_cols entries")
+        other = other.contiguous()
+    if moments is None:
+        moments = torch.empty((n_rows, len(RATING_MOMENTS)), dtype=torch.float64, device=dev)
+    if total is None:
+        total = torch.empty(len(RATING_MOMENTS), dtype=torch.float64, device=dev)
+    off = _host_f64(offset)
+    w = ws.get(L.als_rating_stats_scratch_bytes(nnz, n_rows))
+    check(L.als_row_moments(ptr(row_ptr), ptr(col), ptr(val), nnz, n_rows, int(n_cols),
+                            ptr(other), ctypes.addressof(off), ptr(moments), ptr(total), ptr(w),
+                            w.numel(), stream_ptr(dev)), "als_row_moments")
+    return moments, total
+
+
+def bias_update(moments: torch.Tensor, damping: float, out: Optional[torch.Tensor] = None
+                ) -> torch.Tensor:
+    """sum_row / (damping + n_row) of a moments table (als_bias_update): f64 [n_rows], 0 for a
+    row without ratings."""
+    L = _lib.lib()
+    n_rows = int(moments.shape[0])
+    if out is None:
+        out = torch.empty(n_rows, dtype=torch.float64, device=moments.device)
+    d = _host_f64(damping)
+    check(L.als_bias_update(ptr(moments), n_rows, ctypes.addressof(d), ptr(out),
+                            stream_ptr(moments.device)), "als_bias_update")
+    return out
+
+
+def baseline_predict_rows(urow: torch.Tensor, irow: torch.Tensor, mu: float,
+                          bu: Optional[torch.Tensor], bi: Optional[torch.Tensor], n_users: int,
+                          n_items: int):
+    """mu + bu[urow] + bi[irow] for pairs of dense rows (int32; a row outside its table, -1
+    included, is an unknown id and adds nothing): (pred f32 [n], known uint8 [n], bit 0 = user
+    known, bit 1 = item known).  bu / bi: f64 device tables or None (all zero)."""
+    L = _lib.lib()
+    dev = urow.device
+    urow, irow = urow.to(torch.int32).contiguous(), irow.to(torch.int32).contiguous()
+    if urow.shape != irow.shape or urow.dim() != 1:
+        raise ValueError("baseline_predict_rows: urow and irow must be vectors of one length")
+    n = int(urow.numel())
+    pred = torch.empty(n, dtype=torch.float32, device=dev)
+    known = torch.empty(n, dtype=torch.uint8, device=dev)
+    m = _host_f64(mu)
+    check(L.als_baseline_predict(ptr(urow), ptr(irow), n, ctypes.addressof(m), ptr(bu),
+                                 int(n_users), ptr(bi), int(n_items), ptr(pred), ptr(known),
+                                 stream_ptr(dev)), "als_baseline_predict")
+    return pred, known
+
+
+def rating_stats_dict(moments: torch.Tensor) -> dict:
+    """count (int64), mean, std (population), std_sample (n - 1 in the denominator, NaN where
+    n <= 1), min and max of each row of a moments table; mean and the rest are NaN for a row
+    without ratings.  Device tensors."""
+    n, s, m2 = moments[:, 0], moments[:, 1], moments[:, 2]
+    nan = torch.full_like(n, float("nan"))
+    has = n > 0
+    return {"count": n.to(torch.int64), "mean": torch.where(has, s / n, nan),
+            "std": torch.where(has, torch.sqrt(m2 / n), nan),
+            "std_sample": torch.where(n > 1, torch.sqrt(m2 / (n - 1)), nan),
+            "min": moments[:, 3].clone(), "max": moments[:, 4].clone()}
+
+
+class Baseline:
+    """A fitted mean / bias predictor mu + b_u + b_i (ALSCore.fit_baseline): mu a float, bu /
+    bi f64 device tables in dense order (zeros where the method fits none), uidx / iidx the
+    id maps, history the training objective after every sweep."""
+
+    def __init__(self, method, mu, bu, bi, uidx: IdIndex, iidx: IdIndex, history, ws: Workspace,
+                 reg_user: float = 0.0, reg_item: float = 0.0):
+        self.method, self.mu, self.bu, self.bi = method, float(mu), bu, bi
+        self.uidx, self.iidx, self.history, self.ws = uidx, iidx, list(history), ws
+        self.reg_user, self.reg_item = float(reg_user), float(reg_item)
+        self.device = bu.device
+
+    def predict(self, users, items, return_known: bool = False):
+        """f32 prediction per pair; an id the fit did not see adds a zero bias, so a pair
+        unknown on both sides gets mu.  return_known: also the uint8 flags (bit 0 = user
+        known, bit 1 = item known)."""
+        u = _to_device(users, torch.int32, self.device)
+        i = _to_device(items, torch.int32, self.device)
+        pred, known = baseline_predict_rows(self.uidx.rows_of(u).to(torch.int32),
+                                            self.iidx.rows_of(i).to(torch.int32), self.mu,
+                                            self.bu, self.bi, self.uidx.n, self.iidx.n)
+        return (pred, known) if return_known else pred
+
+    def regression_metrics(self, users, items, ratings, through_origin: bool = False) -> dict:
+        """regression_dict's keys for the predictions against held-out ratings, every pair
+        used (dropped = 0): the moments are K8's column form over (ratings, predict())."""
+        r = _to_device(ratings, torch.float32, self.device)
+        pred = self.predict(users, items)
+        if r.numel() != pred.numel():
+            raise ValueError("users, items and ratings must have the same length")
+        m = regression_moments_cols(r.double(), pred.double(), self.ws)
+        return regression_dict(m.tolist(), through_origin)
+
+
+# ---------------------------------------------------------------------------
 # The engine
 # ---------------------------------------------------------------------------
 def make_engine(users, items, ratings, device=None):
@@ -2114,6 +2252,99 @@ class ALSCore:
         m = regression_moments_pairs(u, i, r, self.uidx, self.iidx, self.U, self.V, self.rank,
                                      self.ws)
         return regression_dict(m.tolist(), through_origin)
+
+    # ---- K16: rating statistics and bias baselines ----
+    def _stats_block(self, user_side: bool, what: str) -> RatingBlock:
+        block = self.user_block if user_side else self.item_block
+        if block is None:
+            raise ValueError(f"{what} needs the training ratings: a core built from_factors "
+                             "holds none")
+        return block
+
+    def rating_stats(self, user_side: bool = False) -> dict:
+        """Per-row statistics of the training ratings (K16; getCountsAndAverages plus spread
+        and range), items by default: {"ids", "count", "mean", "std", "std_sample", "min",
+        "max"} as rating_stats_dict defines them, device tensors in dense (ascending id)
+        order."""
+        block = self._stats_block(user_side, "rating_stats")
+        mom, _ = row_moments(block, self.n_items if user_side else self.n_users, self.ws)
+        out = {"ids": (self.uidx if user_side else self.iidx).ids()}
+        out.update(rating_stats_dict(mom))
+        return out
+
+    def global_stats(self) -> dict:
+        """{count, mean, std, min, max} of all training ratings (std: population), host
+        numbers."""
+        block = self._stats_block(False, "global_stats")
+        _, total = row_moments(block, self.n_users, self.ws)
+        n, s, m2, lo, hi = total.tolist()
+        return {"count": int(n), "mean": s / n if n else float("nan"),
+                "std": math.sqrt(m2 / n) if n else float("nan"), "min": lo, "max": hi}
+
+    def top_rated(self, num: int, min_count: int = 0, user_side: bool = False,
+                  damping: float = 0.0):
+        """The `num` rows with more than `min_count` ratings (strictly) and the highest
+        sum / (damping + count) — the plain mean at damping 0 — highest first, ties to the
+        smaller id: (ids, means, counts), device tensors."""
+        if int(num) < 0 or float(damping) < 0:
+            raise ValueError("top_rated: num and damping must be >= 0")
+        block = self._stats_block(user_side, "top_rated")
+        mom, _ = row_moments(block, self.n_items if user_side else self.n_users, self.ws)
+        n, s = mom[:, 0], mom[:, 1]
+        keep = ((n > float(min_count)) & (n > 0)).nonzero().flatten()   # dense = ascending id
+        score = s[keep] / (float(damping) + n[keep])
+        order = torch.sort(score, descending=True, stable=True).indices[:int(num)]
+        rows = keep[order]
+        return ((self.uidx if user_side else self.iidx).ids()[rows], score[order],
+                n[rows].to(torch.int64))
+
+    def fit_baseline(self, method: str = "bias", reg_user: float = 10.0, reg_item: float = 25.0,
+                     sweeps: int = 10) -> Baseline:
+        """The mean / damped-bias predictor of the training ratings (K16):
+          "global"  mu, the training mean (RecommenderSystem.py:172-177)
+          "item"    mu + b_i, b_i = sum_i (r - mu) / (reg_item + n_i)
+          "user"    mu + b_u, b_u = sum_u (r - mu) / (reg_user + n_u)
+          "bias"    mu + b_u + b_i: `sweeps` times (b_i given b_u, then b_u given b_i) from zero
+        Each update minimises SSE + reg_user sum b_u^2 + reg_item sum b_i^2 over its table
+        exactly, so Baseline.history (that objective after every sweep; one entry for the
+        other methods) never rises.  It comes from the sweep's own moments — a row updated to b
+        keeps M2_row + n_row (mean_row - b)^2 of squared error — with no further pass over
+        the ratings."""
+        if method not in BASELINE_METHODS:
+            raise ValueError(f"method must be one of {BASELINE_METHODS}, got {method!r}")
+        if float(reg_user) < 0 or float(reg_item) < 0 or int(sweeps) < 1:
+            raise ValueError("fit_baseline: reg_user, reg_item must be >= 0 and sweeps >= 1")
+        ib = self._stats_block(False, "fit_baseline")
+        ub = self._stats_block(True, "fit_baseline")
+        f64 = dict(dtype=torch.float64, device=self.device)
+        bu, bi = torch.zeros(self.n_users, **f64), torch.zeros(self.n_items, **f64)
+        _, total = row_moments(ib, self.n_users, self.ws)
+        n, s, m2 = total.tolist()[:3]
+        mu = s / n
+
+        def update(block, n_cols, other, damping, out):
+            mom, _ = row_moments(block, n_cols, self.ws, other=other, offset=mu)
+            bias_update(mom, damping, out=out)
+            cnt, mean = mom[:, 0], torch.where(mom[:, 0] > 0, mom[:, 1] / mom[:, 0], 0.0)
+            return (mom[:, 2] + cnt * (mean - out) ** 2).sum()
+
+        history = []
+        if method == "global":
+            history.append(m2)
+        elif method == "item":
+            sse = update(ib, self.n_users, None, reg_item, bi)
+            history.append(float(sse + reg_item * (bi * bi).sum()))
+        elif method == "user":
+            sse = update(ub, self.n_items, None, reg_user, bu)
+            history.append(float(sse + reg_user * (bu * bu).sum()))
+        else:
+            for _ in range(int(sweeps)):
+                update(ib, self.n_users, bu, reg_item, bi)
+                sse = update(ub, self.n_items, bi, reg_user, bu)
+                history.append(float(sse + reg_user * (bu * bu).sum()
+                                     + reg_item * (bi * bi).sum()))
+        return Baseline(method, mu, bu, bi, self.uidx, self.iidx, history, self.ws,
+                        reg_user, reg_item)
 
     def recommend_users(self, top: int):
         """For every user (dense order): top items as (item ids, scores)."""

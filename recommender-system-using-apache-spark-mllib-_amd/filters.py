@@ -178,6 +178,15 @@ def reject_sharded_list_metrics() -> None:
         "with popularity=)")
 
 
+def reject_sharded_rating_stats() -> None:
+    """The sharded engine carries rating_stats / global_stats / top_rated / fit_baseline with
+    the single-GPU signature and refuses them, as it refuses list_metrics."""
+    raise NotImplementedError(
+        "rating_stats / global_stats / top_rated / fit_baseline are not supported by the "
+        "sharded engine (ShardedALS) yet: rating statistics and bias baselines run on the "
+        "single-GPU engine, an ALSCore built on the same ratings")
+
+
 def reject_sharded_regression() -> None:
     """The sharded engine carries regression_metrics with the single-GPU signature and
     refuses it, as it refuses rank_metrics."""

@@ -20,7 +20,7 @@ from .. import engine as _engine
 from .._data import check_integers, columns_of, to_float32
 from .param import Param
 
-__all__ = ["ALS", "ALSModel"]
+__all__ = ["ALS", "ALSModel", "BaselinePredictor", "BaselineModel"]
 
 _DEFAULT_SEED = zlib.crc32(b"org.apache.spark.ml.recommendation.ALS")
 _COLD = ("nan", "drop")
@@ -373,6 +373,53 @@ class ALSModel:
         u, i, r = columns_of(dataset, (p["userCol"], p["itemCol"], ratingCol or p["ratingCol"]))
         return self._core.regression_metrics(check_integers(u, p["userCol"]),
                                              check_integers(i, p["itemCol"]), to_float32(r))
+
+    # -- K16: what the training ratings themselves say --
+    def _statistics_df(self, user_side: bool):
+        import pandas as pd
+        st = self._core.rating_stats(user_side=user_side)
+        col = {k: st[k].cpu().numpy() for k in ("ids", "count", "mean", "std_sample", "min", "max")}
+        return pd.DataFrame({"id": col["ids"], "count": col["count"], "mean": col["mean"],
+                             "stddev": col["std_sample"], "min": col["min"], "max": col["max"]})
+
+    def itemStatistics(self):
+        """A DataFrame [id, count, mean, stddev, min, max] of the training ratings of every
+        item, ascending id (K16, one sweep on the device; stddev is the sample standard
+        deviation of Spark's describe(), NaN for a single rating).  Raises ValueError on a
+        loaded model, which holds no training data."""
+        return self._statistics_df(False)
+
+    def userStatistics(self):
+        """itemStatistics for the users."""
+        return self._statistics_df(True)
+
+    def topRatedItems(self, numItems: int, minCount: int = 0, damping: float = 0.0):
+        """The reference's "movies with highest average rating and more than 500 reviews"
+        (RecommenderSystem.py:75-86): a DataFrame [id, mean, count] of the numItems items with
+        more than minCount training ratings, by descending sum / (damping + count), ties to
+        the smaller id."""
+        import pandas as pd
+        ids, means, counts = self._core.top_rated(int(numItems), int(minCount), False,
+                                                  float(damping))
+        return pd.DataFrame({"id": ids.cpu().numpy(), "mean": means.cpu().numpy(),
+                             "count": counts.cpu().numpy()})
+
+    def compareToBaseline(self, dataset, method: str = "bias", regUser: float = 10.0,
+                          regItem: float = 25.0, maxIter: int = 10,
+                          ratingCol: Optional[str] = None) -> dict:
+        """The model beside a trivial predictor fitted on the same training ratings
+        (RecommenderSystem.py:167-177 in one call): {"model": evaluateRegression(dataset),
+        "baseline": the same dict for ALSCore.fit_baseline(method, ...), every row used,
+        "rmseRatio": model rmse / baseline rmse}."""
+        p = self._p
+        u, i, r = columns_of(dataset, (p["userCol"], p["itemCol"], ratingCol or p["ratingCol"]))
+        u, i, r = check_integers(u, p["userCol"]), check_integers(i, p["itemCol"]), to_float32(r)
+        base = self._core.fit_baseline(method, float(regUser), float(regItem), int(maxIter))
+        mine = self._core.regression_metrics(u, i, r)
+        theirs = base.regression_metrics(u, i, r)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ratio = float(np.float64(mine["rmse"]) / np.float64(theirs["rmse"]))
+        return {"model": mine, "baseline": theirs, "rmseRatio": ratio}
 
     def evaluateRanking(self, dataset, k: int, *, ratingThreshold: Optional[float] = None,
                         exclude=None, candidates=None) -> dict:
@@ -761,3 +808,150 @@ class ALSModel:
         keys = keys.cpu().numpy() if isinstance(keys, torch.Tensor) else keys
         return pd.DataFrame({key_col: keys, "novelty": pr[:, 0], "averagePopularity": pr[:, 1],
                              "longTailShare": pr[:, 2]})
+
+
+# ---------------------------------------------------------------------------
+# K16: the baseline a recommender is judged against
+# ---------------------------------------------------------------------------
+_BASE_COLD = ("fallback", "nan", "drop")
+
+
+class BaselinePredictor:
+    """mu + b_u + b_i with damped biases (Koren's baseline predictor), fitted on the device
+    (ALSCore.fit_baseline).  method: "global" (the training mean, RecommenderSystem.py:172-177),
+    "item", "user" or "bias" (maxIter alternating sweeps).  regUser / regItem are the damping
+    terms.  An estimator like ALS: fit(dataset, params), copy(extra), get/set accessors, and
+    BaselinePredictor.regItem etc. as the keys of a param map, so TrainValidationSplit and
+    CrossValidator take it as they take any estimator."""
+
+    _defaults = dict(method="bias", regUser=10.0, regItem=25.0, maxIter=10, userCol="user",
+                     itemCol="item", ratingCol="rating", predictionCol="prediction",
+                     coldStartStrategy="fallback")
+
+    def __init__(self, **kw):
+        unknown = set(kw) - set(self._defaults)
+        if unknown:
+            raise TypeError(f"unexpected keyword argument(s): {sorted(unknown)}")
+        self._p = dict(self._defaults)
+        self._p.update(kw)
+
+    def getOrDefault(self, name):
+        return self._p[name.name if isinstance(name, Param) else name]
+
+    _param_map = classmethod(ALS._param_map.__func__)
+
+    def copy(self, extra=None) -> "BaselinePredictor":
+        other = BaselinePredictor(**self._p)
+        other._p.update(self._param_map(extra))
+        return other
+
+    @staticmethod
+    def _validate(p: dict) -> None:
+        if p["method"] not in _engine.BASELINE_METHODS:
+            raise ValueError(f"method must be one of {_engine.BASELINE_METHODS}, got "
+                             f"{p['method']!r}")
+        if not float(p["regUser"]) >= 0 or not float(p["regItem"]) >= 0:
+            raise ValueError("regUser and regItem must be >= 0")
+        if not isinstance(p["maxIter"], (int, np.integer)) or p["maxIter"] < 1:
+            raise ValueError(f"maxIter must be an integer >= 1, got {p['maxIter']!r}")
+        if str(p["coldStartStrategy"]).lower() not in _BASE_COLD:
+            raise ValueError(f"coldStartStrategy given invalid value {p['coldStartStrategy']} "
+                             f"(supported: {', '.join(_BASE_COLD)})")
+
+    def fit(self, dataset, params=None):
+        """Fit on `dataset`; params as ALS.fit takes them (a map, or a list of maps)."""
+        if isinstance(params, (list, tuple)):
+            return [self.fit(dataset, m) for m in params]
+        if params is not None:
+            return self.copy(params).fit(dataset)
+        p = self._p
+        self._validate(p)
+        u, i, r = columns_of(dataset, (p["userCol"], p["itemCol"], p["ratingCol"]))
+        core = _engine.make_engine(check_integers(u, p["userCol"]),
+                                   check_integers(i, p["itemCol"]), to_float32(r))
+        base = core.fit_baseline(p["method"], float(p["regUser"]), float(p["regItem"]),
+                                 int(p["maxIter"]))
+        return BaselineModel(base, dict(p))
+
+
+_make_accessors(BaselinePredictor, list(BaselinePredictor._defaults))
+for _name in BaselinePredictor._defaults:
+    setattr(BaselinePredictor, _name, Param("BaselinePredictor", _name))
+del _name
+
+
+class BaselineModel:
+    """A fitted BaselinePredictor: globalMean, userBias / itemBias, transform and
+    evaluateRegression.  Save / load are not offered."""
+
+    def __init__(self, baseline: "_engine.Baseline", params: dict):
+        self._base = baseline
+        self._p = params
+
+    @property
+    def baseline(self) -> "_engine.Baseline":
+        return self._base
+
+    @property
+    def globalMean(self) -> float:
+        return self._base.mu
+
+    @property
+    def objectiveHistory(self):
+        """SSE + regUser sum b_u^2 + regItem sum b_i^2 on the training data after every
+        sweep."""
+        return list(self._base.history)
+
+    def _bias_df(self, idx, b):
+        import pandas as pd
+        return pd.DataFrame({"id": idx.ids().cpu().numpy(), "bias": b.cpu().numpy()})
+
+    @property
+    def userBias(self):
+        return self._bias_df(self._base.uidx, self._base.bu)
+
+    @property
+    def itemBias(self):
+        return self._bias_df(self._base.iidx, self._base.bi)
+
+    def setColdStartStrategy(self, v):
+        if str(v).lower() not in _BASE_COLD:
+            raise ValueError(f"coldStartStrategy given invalid value {v} (supported: "
+                             f"{', '.join(_BASE_COLD)})")
+        self._p["coldStartStrategy"] = v
+        return self
+
+    def setPredictionCol(self, v):
+        self._p["predictionCol"] = v
+        return self
+
+    def transform(self, dataset):
+        """Append the prediction column (fp32).  coldStartStrategy "fallback": an unknown user
+        or item adds a zero bias, so no row is NaN and a pair unknown on both sides gets
+        globalMean; "nan": NaN where either id is unknown, as ALSModel; "drop": those rows
+        dropped."""
+        import pandas as pd
+        p = self._p
+        u, i = columns_of(dataset, (p["userCol"], p["itemCol"]))
+        u, i = check_integers(u, p["userCol"]), check_integers(i, p["itemCol"])
+        pred, known = self._base.predict(u, i, return_known=True)
+        pred, known = pred.cpu().numpy(), known.cpu().numpy()
+        cold = str(p["coldStartStrategy"]).lower()
+        if cold != "fallback":
+            pred = np.where(known == 3, pred, np.float32("nan"))
+        if isinstance(dataset, pd.DataFrame):
+            out = dataset.copy()
+        else:
+            out = pd.DataFrame({p["userCol"]: u, p["itemCol"]: i})
+        out[p["predictionCol"]] = pred
+        if cold == "drop":
+            out = out[known == 3]
+        return out
+
+    def evaluateRegression(self, dataset, ratingCol: Optional[str] = None) -> dict:
+        """ALSModel.evaluateRegression's dict for the baseline's predictions; every row is
+        used (the fallback prediction), so "dropped" is 0."""
+        p = self._p
+        u, i, r = columns_of(dataset, (p["userCol"], p["itemCol"], ratingCol or p["ratingCol"]))
+        return self._base.regression_metrics(check_integers(u, p["userCol"]),
+                                             check_integers(i, p["itemCol"]), to_float32(r))

@@ -28,7 +28,7 @@ import numpy as np
 from .. import engine as _engine
 from .._data import check_integers, columns_of, to_float32
 
-__all__ = ["ALS", "MatrixFactorizationModel", "Rating"]
+__all__ = ["ALS", "BaselineModel", "MatrixFactorizationModel", "Rating"]
 
 _DEFAULT_SEED = zlib.crc32(b"org.apache.spark.mllib.recommendation.ALS")
 
@@ -107,6 +107,21 @@ class MatrixFactorizationModel:
         left out and counted in "dropped" (predictAll's inner join)."""
         u, i, r = _triples(ratings)
         return self._core.regression_metrics(u, i, r)
+
+    def _statistics(self, user_side: bool):
+        st = self._core.rating_stats(user_side=user_side)
+        ids, cnt, mean = (st[k].cpu().numpy() for k in ("ids", "count", "mean"))
+        return [(int(a), int(c), float(m)) for a, c, m in zip(ids, cnt, mean)]
+
+    def productStatistics(self):
+        """[(product, number of ratings, average rating)] of the training ratings, ascending
+        id — the reference's getCountsAndAverages (RecommenderSystem.py:50-66) in one sweep on
+        the device (K16).  Raises ValueError on a loaded model, which holds no ratings."""
+        return self._statistics(False)
+
+    def userStatistics(self):
+        """productStatistics for the users."""
+        return self._statistics(True)
 
     def trainingObjective(self, lambda_: float, implicit: bool = False,
                           alpha: float = 0.01) -> dict:
@@ -404,6 +419,51 @@ class ALS:
                  float(alpha) if implicitPrefs else 1.0,
                  seed=_DEFAULT_SEED if seed is None else int(seed), nonnegative=True)
         return MatrixFactorizationModel(core)
+
+
+class BaselineModel:
+    """The mean / damped-bias predictor mu + b_u + b_i of (user, product, rating) rows (K16,
+    ALSCore.fit_baseline): what the reference's "Comparing your model" step
+    (RecommenderSystem.py:172-177) measures a factor model against.  An id the training rows
+    do not hold adds a zero bias, so every pair has a prediction."""
+
+    def __init__(self, baseline: "_engine.Baseline"):
+        self._base = baseline
+
+    @classmethod
+    def train(cls, ratings, method: str = "bias", regUser: float = 10.0, regItem: float = 25.0,
+              iterations: int = 10) -> "BaselineModel":
+        """method: "global" (the training mean), "item", "user" or "bias" (`iterations`
+        alternating sweeps of the damped item and user biases)."""
+        u, i, r = _triples(ratings)
+        core = _engine.make_engine(u, i, r)
+        return cls(core.fit_baseline(method, float(regUser), float(regItem), int(iterations)))
+
+    @property
+    def baseline(self) -> "_engine.Baseline":
+        return self._base
+
+    @property
+    def globalMean(self) -> float:
+        return self._base.mu
+
+    def predict(self, user: int, product: int) -> float:
+        p = self._base.predict(np.array([user], np.int32), np.array([product], np.int32))
+        return float(p.cpu().numpy()[0])
+
+    def predictAll(self, user_product) -> List[Rating]:
+        """A Rating for every (user, product) pair, unknown ids included."""
+        u, i = _pairs(user_product)
+        if len(u) == 0:
+            return []
+        p = self._base.predict(u, i).cpu().numpy()
+        return [Rating(int(a), int(b), float(c)) for a, b, c in zip(u, i, p)]
+
+    def regressionMetrics(self, ratings) -> dict:
+        """MatrixFactorizationModel.regressionMetrics' dict for the baseline; no row is
+        dropped."""
+        u, i, r = _triples(ratings)
+        return self._base.regression_metrics(u, i, r)
 
 
 def compute_error(predicted: Iterable, actual: Iterable) -> float:

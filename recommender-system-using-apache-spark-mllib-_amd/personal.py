@@ -9,6 +9,7 @@ RecommenderSystem.py:227-249, restated for the MI355X engine:
   R:242-245 join with counts and titles, keep NumRating > 75
   R:247  takeOrdered(20, key=-prediction)
 
+`highest_rated_movies` is the script's first part (R:49-86) on the device (K16).
 `movie_counts_and_averages` is R:50-58's getCountsAndAverages over the full ratings
 (the count the R:245 filter reads).  Ties in the prediction keep moviesRDD order
 (takeOrdered is heapq.nsmallest over the partitions: stable for equal keys).
@@ -19,7 +20,7 @@ from typing import Dict, Iterable, List, Sequence, Tuple
 
 import numpy as np
 
-__all__ = ["movie_counts_and_averages", "personal_recommendations",
+__all__ = ["movie_counts_and_averages", "highest_rated_movies", "personal_recommendations",
            "personal_recommendations_fold_in", "personal_explanations", "similar_movies"]
 
 
@@ -33,6 +34,37 @@ def movie_counts_and_averages(ratings) -> Dict[int, Tuple[int, float]]:
     ids, inv, cnt = np.unique(m, return_inverse=True, return_counts=True)
     tot = np.bincount(inv, weights=r)
     return {int(a): (int(c), float(t) / int(c)) for a, c, t in zip(ids, cnt, tot)}
+
+
+def highest_rated_movies(source, movies: Iterable[Sequence], min_count: int = 500,
+                         num: int = 20) -> List[Tuple[float, str, int]]:
+    """R:75-86, "movies with highest average rating and more than 500 reviews": (average
+    rating, movie name, number of ratings) of the `num` movies of `movies` with MORE than
+    `min_count` ratings, highest average first, equal averages by ascending MovieID.  Counts
+    and sums come from one sweep of the item-side ratings on the device (K16,
+    ALSCore.top_rated).
+
+    source: a fitted model (MatrixFactorizationModel / ALSModel), an ALSCore, or raw (user,
+            movie, rating) triples, from which an engine is built
+    movies: (MovieID, title) pairs (moviesRDD, R:39); a rated movie without a title is left
+            out, as R:71's join does."""
+    from . import engine as _engine
+    if isinstance(source, _engine.ALSCore):
+        eng = source
+    elif getattr(source, "engine", None) is not None:
+        eng = source.engine
+    else:
+        from ._data import check_integers, columns_of, to_float32
+        u, m, r = columns_of(source, ("user", "movie", "rating"))
+        eng = _engine.ALSCore(check_integers(u, "user"), check_integers(m, "movie"),
+                              to_float32(r))
+    titles = {}
+    for m, t in movies:
+        titles.setdefault(int(m), str(t))
+    ids, means, counts = (x.cpu().numpy() for x in eng.top_rated(eng.n_items, int(min_count)))
+    out = [(float(a), titles[int(m)], int(c)) for m, a, c in zip(ids, means, counts)
+           if int(m) in titles]
+    return out[:int(num)]
 
 
 def _engine_of(model):
