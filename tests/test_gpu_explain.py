@@ -17,7 +17,7 @@ import torch
 
 import explain_ref as R
 from als_mi355x import engine as E
-from helpers import report
+from helpers import explain_check_slots, explain_reference, ragged_csr, ragged_ptr, report
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -78,30 +78,9 @@ def _targets(rows, counts, seed=0):
     return out
 
 
-def _csr(rows):
-    lens = np.array([len(c) for c, _ in rows], np.int64)
-    ptr = np.zeros(len(rows) + 1, np.int64)
-    np.cumsum(lens, out=ptr[1:])
-    col = np.concatenate([np.asarray(c, np.int64) for c, _ in rows] + [np.zeros(0, np.int64)])
-    val = np.concatenate([np.asarray(v, np.float32) for _, v in rows] + [np.zeros(0, np.float32)])
-    return ptr, col.astype(np.int32), val.astype(np.float32)
-
-
-def _ragged(lists):
-    ptr = np.zeros(len(lists) + 1, np.int64)
-    np.cumsum([len(x) for x in lists], out=ptr[1:])
-    return ptr, np.concatenate([np.asarray(x, np.int64) for x in lists]
-                               + [np.zeros(0, np.int64)]).astype(np.int32)
-
-
-def _reference(rows, targets, V, reg, implicit, alpha):
-    """Per slot (row, target, score, pos, contrib) with the full ordered list."""
-    yty = V.astype(np.float64).T @ V.astype(np.float64)
-    out = []
-    for r, ((c, v), tg) in enumerate(zip(rows, targets)):
-        for t, (s, pos, con) in zip(tg, R.explain_row(c, v, V, tg, reg, implicit, alpha, yty)):
-            out.append((r, int(t), s, pos, con))
-    return out
+_csr = ragged_csr
+_ragged = ragged_ptr
+_reference = explain_reference   # per slot (row, target, score, pos, contrib), the full list
 
 
 def _run(rows, targets, V, k, reg, implicit, top_n, alpha=ALPHA, ld=None, fill=0.0, fold=False):
@@ -141,24 +120,7 @@ def _parity_case(k, implicit):
     return V, rows, targets, ref
 
 
-def _check_slots(ref, rows, V, k, reg, implicit, alpha, sc, pos, con, top_n):
-    """Compare one call's outputs with the reference slots; returns (max contribution
-    error, max score error)."""
-    Vd, sc = V.astype(np.float64), sc.astype(np.float64)
-    xs = [R.solve_row(c, v, V, reg, implicit, alpha) for c, v in rows]
-    e_c = e_s = 0.0
-    for s, (r, t, s_ref, p_ref, c_ref) in enumerate(ref):
-        n = min(top_n, len(p_ref))
-        np.testing.assert_array_equal(pos[s, :n], p_ref[:n], err_msg=f"slot {s} row {r}")
-        assert (pos[s, n:] == -1).all() and (con[s, n:] == 0).all()
-        if len(p_ref) == 0:
-            assert sc[s] == 0
-            continue
-        whole = len(p_ref) <= top_n      # the full vector, or the listed head of a longer row
-        den = np.linalg.norm(c_ref if whole else c_ref[:n])
-        e_c = max(e_c, np.linalg.norm(con[s, :n] - c_ref[:n]) / max(den, 1e-300))
-        e_s = max(e_s, abs(sc[s] - s_ref) / (np.linalg.norm(xs[r]) * np.linalg.norm(Vd[t])))
-    return e_c, e_s
+_check_slots = explain_check_slots   # -> (max contribution error, max score error)
 
 
 # ------------------------------------------------------------------ kernel

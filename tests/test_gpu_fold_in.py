@@ -16,8 +16,7 @@ import pytest
 import torch
 
 from als_mi355x import engine as E
-from helpers import rel_row_errs, report
-from oracle import als_oracle as O
+from helpers import fold_in_oracle, ragged_csr, rel_row_errs, report
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -58,26 +57,8 @@ def _rows(k, seed=0):
     return rows
 
 
-def _csr(rows):
-    lens = np.array([len(c) for c, _ in rows], np.int64)
-    ptr = np.zeros(len(rows) + 1, np.int64)
-    np.cumsum(lens, out=ptr[1:])
-    col = np.concatenate([np.asarray(c, np.int64) for c, _ in rows] + [np.zeros(0, np.int64)])
-    val = np.concatenate([np.asarray(v, np.float32) for _, v in rows] + [np.zeros(0, np.float32)])
-    return ptr, col.astype(np.int32), val.astype(np.float32)
-
-
-def _oracle(rows, V, reg, implicit, alpha):
-    """(X_ref [n, k] with zero rows where nothing is used, n_used [n])."""
-    known = [(np.asarray(c)[(np.asarray(c) >= 0) & (np.asarray(c) < len(V))],
-              np.asarray(v)[(np.asarray(c) >= 0) & (np.asarray(c) < len(V))]) for c, v in rows]
-    n_used = np.array([len(c) for c, _ in known], np.int64)
-    full = np.nonzero(n_used > 0)[0]
-    ref = np.zeros((len(rows), V.shape[1]), np.float32)
-    if len(full):
-        ptr, col, val = _csr([known[r] for r in full])
-        ref[full] = O.half_sweep(ptr, col, val, V, reg, implicit, alpha)
-    return ref, n_used
+_csr = ragged_csr
+_oracle = fold_in_oracle   # (X_ref [n, k] with zero rows where nothing is used, n_used [n])
 
 
 def _run(rows, V, k, reg, implicit, alpha=ALPHA, ld=None, fill=0.0):

@@ -19,7 +19,7 @@ import torch
 
 import nnls_ref as R
 from als_mi355x import engine as E
-from helpers import rel_row_errs, report
+from helpers import nnls_sources, ragged_csr, rel_row_errs, report
 from oracle import als_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -33,13 +33,7 @@ SOURCES = pytest.mark.parametrize("signed", [True, False], ids=["signed", "abs"]
 
 
 # ------------------------------------------------------------------ helpers
-def _sources(k, signed, seed=0):
-    """Unit-norm source rows: signed (about half of a solution's coordinates end on the wall)
-    or their absolute values (few do)."""
-    rng = np.random.default_rng(3000 + 7 * k + seed)
-    Y = rng.standard_normal((N_SRC, k))
-    Y /= np.linalg.norm(Y, axis=1, keepdims=True)
-    return (Y if signed else np.abs(Y)).astype(np.float32)
+_sources = nnls_sources   # unit-norm rows of N_SRC sources, signed or their absolute values
 
 
 def _rows(k, seed=0):
@@ -56,13 +50,7 @@ def _rows(k, seed=0):
     return rows
 
 
-def _csr(rows):
-    lens = np.array([len(c) for c, _ in rows], np.int64)
-    ptr = np.zeros(len(rows) + 1, np.int64)
-    np.cumsum(lens, out=ptr[1:])
-    col = np.concatenate([np.asarray(c, np.int64) for c, _ in rows] + [np.zeros(0, np.int64)])
-    val = np.concatenate([np.asarray(v, np.float32) for _, v in rows] + [np.zeros(0, np.float32)])
-    return ptr, col.astype(np.int32), val.astype(np.float32)
+_csr = ragged_csr
 
 
 def _dev(M, ld=None, fill=0.0):
