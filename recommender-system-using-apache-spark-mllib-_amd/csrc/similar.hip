@@ -277,8 +277,9 @@ __global__ __launch_bounds__(64) void sim_sweep_kernel(
         ss += __shfl_xor(ss, m);
       }
       const int64_t row = base + rr * G + grp;
-      // a neighbour has a finite, non-zero norm (NaN fails both tests)
-      const bool rowok = row < r1 && ss > 0.f && ss < __builtin_inff();
+      // a neighbour has a finite norm of at least 2^-50 (NaN fails both tests): below that
+      // bound |t|^2 and its partial sums lose bits to the subnormal grid (2^-149 a step)
+      const bool rowok = row < r1 && ss >= 0x1p-100f && ss < __builtin_inff();
       const float invt = 1.f / sqrtf(ss);
 #pragma unroll
       for (int v = 0; v < VPL; ++v) {
