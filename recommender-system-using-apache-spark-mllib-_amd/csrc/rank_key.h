@@ -1,5 +1,5 @@
 // The ranking key and the row filter shared by the ranking kernels: the top-k sweep
-// (topk.hip), the cosine neighbours (similar.hip) and the full-ranking positions
+// (topk_sweep.h), the cosine neighbours (similar.hip) and the full-ranking positions
 // (rank_positions.hip).
 #pragma once
 #include "als_common.h"

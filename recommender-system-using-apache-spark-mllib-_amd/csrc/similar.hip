@@ -56,7 +56,7 @@ constexpr int kSimMergeFan = 32;   // slice lists per first-stage merge group
 
 // Cut log L (n keys, top < n <= 64 J, unique, all > 0; one wavefront, L in LDS) to its `top`
 // largest keys, in place at the front; returns the smallest kept key.  The top-th largest
-// score word first (bitwise search, the method of topk.hip's tk_log_kth), then the index
+// score word first (bitwise search, the method of topk_lists.h's tk_log_kth), then the index
 // word among the keys that tie on it.
 template <int J>
 __device__ __forceinline__ uint64_t sim_compact(uint64_t* __restrict__ L, int n, int top) {

@@ -353,7 +353,7 @@ def topk_sample_check(idx, sc, S, top, adm=None, skip=None):
 # The two-row-group cases of K5 (test_gpu_topk_row_groups.py, test_topk_row_groups_cpu.py).
 # csrc/topk.hip's topk_split_rg takes two row groups (256 query rows per workgroup) for
 # register lists and key logs from kTkRg2MinRows = 262,144 query rows; a key-log launch
-# covers kTkLogBlocks = 512 blocks, 131,072 rows at two groups.
+# covers kTkLogBlocks = 512 blocks (csrc/topk_sweep.h), 131,072 rows at two groups.
 K5RG_MIN_ROWS = 262144
 K5RG_SLICE_ROWS = 131072
 K5RG_NQ = K5RG_MIN_ROWS + 130   # 1,025 blocks; the last: group 0 full, 2 rows of group 1

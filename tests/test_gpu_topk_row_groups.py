@@ -185,7 +185,7 @@ def test_two_row_groups_filtered(rg_case, rank, top):
 
 
 # ------------------------------------------------------------------ 2. edges at one group
-# V rows per tile, (NK, list class): csrc/topk.hip tk_vt — 384 / NK (192 at NK = 4) with
+# V rows per tile, (NK, list class): csrc/topk_sweep.h tk_vt — 384 / NK (192 at NK = 4) with
 # register lists and key logs, 64 / NK with LDS lists.  A change there must change this.
 TILE_ROWS = {(1, "reg"): 384, (2, "reg"): 192, (4, "reg"): 192,
              (1, "lds"): 64, (2, "lds"): 32, (4, "lds"): 16}

@@ -1,8 +1,9 @@
-"""The headers that csrc/gram_solve.hip is made of are self-contained: a translation unit that
-holds nothing but the #include of one of them compiles for gfx950 (syntax only), so each header
-includes what it uses and none leans on the order in which gram_solve.hip includes them.
-gram_solve.hip must include every header of the list, directly or through another, which keeps
-the list from going stale.  CPU only: hipcc cross-compiles."""
+"""The headers that csrc/gram_solve.hip, csrc/topk.hip and csrc/topk_filtered.hip are made of are
+self-contained: a translation unit that holds nothing but the #include of one of them compiles
+for gfx950 (syntax only), so each header includes what it uses and none leans on the order in
+which its translation unit includes them.  Each unit must include every header of its row,
+directly or through another, and nothing else of csrc but the row's shared headers, which keeps
+the table from going stale.  CPU only: hipcc cross-compiles."""
 import os
 import re
 import shutil
@@ -14,8 +15,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "recommender-system-using-apache-spark-mllib-_amd", "csrc")
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
-HEADERS = ["solve_config.h", "gram_accumulate.h", "solve_guards.h", "panel_solve.h", "w1_solve.h",
-           "partial_slots.h", "dual_solve.h", "rescue64.h", "yty.h"]
+# translation unit: (the headers it is made of, the headers of csrc it shares with other kernels'
+# units and that were there before the split)
+UNITS = {
+    "gram_solve.hip": (["solve_config.h", "gram_accumulate.h", "solve_guards.h", "panel_solve.h",
+                        "w1_solve.h", "partial_slots.h", "dual_solve.h", "rescue64.h", "yty.h"],
+                       {"als_common.h", "task_order.h"}),
+    "topk.hip": (["topk_split.h", "topk_prep.h", "topk_lists.h", "topk_sweep.h"],
+                 {"als_common.h", "rank_key.h"}),
+    # the filtered sweep does not prepare V: topk_prep.h is topk.hip's alone
+    "topk_filtered.hip": (["topk_split.h", "topk_lists.h", "topk_sweep.h"],
+                          {"als_common.h", "rank_key.h"}),
+}
+HEADERS = list(dict.fromkeys(h for headers, _ in UNITS.values() for h in headers))
 
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 
@@ -38,10 +50,19 @@ def test_header_compiles_alone(header, tmp_path):
     assert p.returncode == 0, p.stderr[-2000:]
 
 
+def _check_unit(unit):
+    headers, shared = UNITS[unit]
+    reached = _includes(unit, set())
+    assert not [h for h in headers if h not in reached]
+    # and the row names every header the unit is made of: what else it reaches is shared (a
+    # .hip reached through an #include would show here too)
+    assert reached - shared == set(headers)
+
+
 def test_gram_solve_includes_every_header():
-    reached = _includes("gram_solve.hip", set())
-    assert not [h for h in HEADERS if h not in reached]
-    # and the list names every solve header there is: the other headers of csrc are shared
-    # with other translation units and were there before the split
-    others = {"als_common.h", "task_order.h"}
-    assert reached - others == set(HEADERS)
+    _check_unit("gram_solve.hip")
+
+
+@pytest.mark.parametrize("unit", ["topk.hip", "topk_filtered.hip"])
+def test_topk_unit_includes_every_header(unit):
+    _check_unit(unit)

@@ -11,23 +11,16 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "..", "..", "recommender-system-using-apache-spark-mllib-_amd", "csrc")
-GS = "gram_solve.hip"  # and the headers it is made of:
+# headers of gram_solve.hip
 GA, SC, SG, W1, DU = ("gram_accumulate.h", "solve_config.h", "solve_guards.h", "w1_solve.h",
                       "dual_solve.h")
-TK = "topk.hip"
+TK = "topk_sweep.h"  # the top-k sweep kernel (topk.hip and topk_filtered.hip instantiate it)
 
 VARIANTS = {
     "base": [],
-    # round 6: quad top-k lists (16 < top <= 128) with one row group only
-    # round 6: the committed (HEAD) topk.hip in place of the working tree's ("@HEAD" files)
-    "oldtopk": [(TK, "@HEAD", None)],
-    # a candidate topk.hip kept outside the tree (/tmp/topk_cand.hip)
-    "tkcand": [(TK, "@FILE", "/tmp/topk_cand.hip")],
-    "tkprev": [(TK, "@FILE", "/tmp/topk_prev.hip")],
     # top-k register lists: six blocks per ballot (logs keep four: their registers)
     "tk_nb6": [(TK, "constexpr int NB4 = 4;  // blocks per ballot",
                 "constexpr int NB4 = (TOPR > 0 && TOPR <= 16) ? 6 : 4;  // blocks per ballot")],
-    "gsprev": [(GS, "@FILE", "/tmp/gs_prev.hip")],
     # the n x n dual kernel: step s+1's gathers in flight during step s at NB = 6 too
     "dualnb2": [(DU, "constexpr int NBUF = NB <= 4 ? 2 : 1;", "constexpr int NBUF = 2;")],
     # round 6: the LDL^T pivot-spread limit (rows beyond it go to the fp64 rescue)
@@ -92,22 +85,13 @@ def build(tag: str) -> str:
     shutil.copytree(CSRC, src)
     for f, old, new in VARIANTS[tag]:
         p = os.path.join(src, f)
-        if old == "@FILE":  # the whole file from a path (outside the tree: a candidate)
-            shutil.copyfile(new, p)
-            continue
-        if old == "@HEAD":  # the whole file as committed
-            rel = "recommender-system-using-apache-spark-mllib-_amd/csrc/" + f
-            open(p, "w").write(subprocess.check_output(["git", "show", "HEAD:" + rel],
-                                                       cwd=os.path.join(HERE, "..", ".."),
-                                                       text=True))
-            continue
         s = open(p).read()
         if old not in s:
             raise SystemExit(f"{tag}: patch does not apply to {f}: {old[:70]!r}")
         open(p, "w").write(s.replace(old, new))
     objs = []
     procs = []
-    for s in ("csr_build", "gram_solve", "predict", "topk"):
+    for s in ("csr_build", "gram_solve", "predict", "topk", "topk_filtered"):
         o = os.path.join(src, s + ".o")
         objs.append(o)
         procs.append(subprocess.Popen(["/opt/rocm/bin/hipcc", "-O3", "-fPIC", "-std=c++17",
