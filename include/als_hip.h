@@ -447,7 +447,8 @@ int als_full_rank_metrics(const int32_t* above, const int32_t* tied, const int32
  *   out[3] n      ratings            out[4] n_positive  ratings with r > 0
  * Y = NULL: no Y row is read and out[0] = out[1] = 0 (the other side's call for its
  * regulariser: both sides hold the same ratings, so the data term is needed once).  A col
- * outside [0, n_cols) adds no data term and is never dereferenced.  Work is split by
+ * outside [0, n_cols) adds no data term and is never dereferenced; its rating still counts
+ * in n, n_positive and reg (the counts are taken before the range test).  Work is split by
  * ratings, als_objective_span() per block whichever rows they fall in, so one row of 10^5
  * ratings costs per rating what a short one does.  alpha is widened to fp64 from the fp32
  * the solver takes.  Columns [k, ld) of X and Y are ignored.

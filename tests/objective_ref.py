@@ -87,22 +87,27 @@ def objective_dense(users, items, ratings, U, V, reg, alpha=1.0):
     return _pack(data, abs(data), reg, reg_u, reg_i, r)
 
 
-def side(rows, cols, vals, X, Y, implicit=False, alpha=1.0):
+def side(rows, cols, vals, X, Y, implicit=False, alpha=1.0, n_cols=None):
     """What one rating pass over one CSR side returns (als_objective_side's five numbers):
     [sum of the rating terms, sum of their absolute values, sum_row n_row |x_row|^2, ratings,
-    ratings with r > 0]; X = the side's own factors, Y = the other side's (None: no terms)."""
+    ratings with r > 0]; X = the side's own factors, Y = the other side's (None: no terms).
+    n_cols given: a rating whose col is outside [0, n_cols) adds no term to the first two, and
+    still counts in the other three (the contract of include/als_hip.h)."""
     a, b, r, X, _, alpha = _prep(rows, cols, vals, X, X, alpha)
     w = (r > 0).astype(np.float64) if implicit else np.ones_like(r)
     reg = float((np.bincount(a, weights=w, minlength=X.shape[0]) * (X * X).sum(1)).sum())
     if Y is None:
         return [0.0, 0.0, reg, float(len(r)), float((r > 0).sum())]
+    n, n_pos = float(len(r)), float((r > 0).sum())
+    if n_cols is not None:
+        keep = (b >= 0) & (b < n_cols)
+        a, b, r = a[keep], b[keep], r[keep]
     s = (X[a] * np.asarray(Y, np.float32).astype(np.float64)[b]).sum(1)
     if implicit:
         terms = (1.0 + alpha * np.abs(r)) * ((r > 0) - s) ** 2 - s * s
     else:
         terms = (r - s) ** 2
-    return [float(terms.sum()), float(np.abs(terms).sum()), reg, float(len(r)),
-            float((r > 0).sum())]
+    return [float(terms.sum()), float(np.abs(terms).sum()), reg, n, n_pos]
 
 
 GROUPS = 5

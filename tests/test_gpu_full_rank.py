@@ -65,11 +65,16 @@ def _filter_modes(rng, n_q, n_v, rel):
             ("both", dict(ex=ex, allow=allow)))
 
 
-def _check_exact(rng, rank, n_v, n_q, sizes):
+def _check_exact(rng, rank, n_v, n_q, sizes, edit=None):
+    """edit(rel, modes): changes the relevant sets and the filter modes' `ex` / `allow` in
+    place before anything is computed from them."""
     Q, V = F.integer_factors(rng, n_q, rank), F.integer_factors(rng, n_v, rank)
     rel = F.random_relevant(rng, n_q, n_v, sizes)
+    modes = _filter_modes(rng, n_q, n_v, rel)
+    if edit is not None:
+        edit(rel, dict(modes))
     seen_inadmissible = 0
-    for name, kw in _filter_modes(rng, n_q, n_v, rel):
+    for name, kw in modes:
         ref = F.counts(Q, V, rel, **kw)
         above, tied, n_adm, sums, _ = run_kernel(Q, V, rel, **kw)
         np.testing.assert_array_equal(n_adm, ref["n_adm"], err_msg=f"n_adm, {name}")
@@ -135,6 +140,75 @@ def test_exact_counts_for_a_row_larger_than_the_table():
     n_v = table + 150
     sizes = np.array([3, 0, table + 50, 1, 40])
     _check_exact(rng, 5, n_v, 5, sizes)
+
+
+@pytest.mark.parametrize("n_v", [127, 128, 129, 256])
+def test_exact_counts_at_the_sweep_tile_edges(n_v):
+    """The sweep stages V in tiles of 128 rows: one row short of a tile, a full tile, one row
+    into the second, two full tiles.  The allowed set is cut at the 32-bit words of the mask:
+    rows 31 and 33 allowed and 32 not, 63 and 65 not and 64 allowed, and query row 0 holds all
+    six as relevant entries."""
+    edge = {31: True, 32: False, 33: True, 63: False, 64: True, 65: False}
+
+    def edit(rel, modes):
+        rel[0] = np.union1d(rel[0], list(edge)).astype(np.int64)
+        allow = np.setdiff1d(np.union1d(modes["allow"]["allow"], [j for j in edge if edge[j]]),
+                             [j for j in edge if not edge[j]])
+        modes["allow"]["allow"] = modes["both"]["allow"] = allow
+
+    rng = np.random.default_rng(n_v)
+    n_q = 33
+    assert _check_exact(rng, 9, n_v, n_q, rng.integers(0, 10, n_q), edit) >= 3
+
+
+def _table_sizes(total, n_q=32):
+    """n_q uneven row sizes that add up to `total`."""
+    base = total // n_q
+    sizes = np.full(n_q, base)
+    d = np.arange(n_q // 2) % 9
+    sizes[0::2] += d
+    sizes[1::2] -= d
+    sizes[-1] += total - int(sizes.sum())
+    assert int(sizes.sum()) == total and sizes.min() > 0
+    return sizes
+
+
+@pytest.mark.parametrize("over", [0, 1])
+def test_exact_counts_when_a_workgroup_fills_the_table_exactly(over):
+    """The 32 rows of one workgroup hold exactly kRpTable relevant entries (one sweep, and the
+    next pass finds nothing left), and one more (a second sweep for a single entry)."""
+    table = E.rank_positions_table()
+    sizes = _table_sizes(table + over)
+    rng = np.random.default_rng(80 + over)
+    _check_exact(rng, 7, int(sizes.max()) + 40, 32, sizes)
+
+
+@pytest.mark.parametrize("tables", [1, 2])
+def test_exact_counts_for_a_row_of_whole_tables(tables):
+    """A single row of exactly kRpTable entries, and of exactly two tables' worth: its passes
+    end on the table's last slot, and the rows after it wait for a pass of their own."""
+    table = E.rank_positions_table()
+    rng = np.random.default_rng(82 + tables)
+    sizes = np.array([0, tables * table, 0, 0, 5 * (tables - 1)])
+    _check_exact(rng, 5, tables * table + 10, 5, sizes)
+
+
+def test_relevant_and_excluded_entries_outside_the_catalogue():
+    """Relevant entries -1 and n_v come back as -1 and count as inadmissible; exclusion entries
+    -1, n_v and n_v + 5 exclude nothing."""
+    n_v, n_q = 129, 37
+
+    def edit(rel, modes):
+        for r in range(0, n_q, 3):
+            rel[r] = np.concatenate([[-1], rel[r], [n_v]]).astype(np.int64)
+        rel[1] = np.array([-1, n_v], np.int64)             # nothing but such entries
+        ex = modes["exclude"]["ex"]
+        for r in range(0, n_q, 2):
+            ex[r] = np.concatenate([[-1, -1], ex[r], [n_v, n_v + 5]]).astype(np.int64)
+        assert modes["both"]["ex"] is ex
+
+    rng = np.random.default_rng(84)
+    assert _check_exact(rng, 9, n_v, n_q, rng.integers(0, 10, n_q), edit) >= 4 * (2 * 13 + 1)
 
 
 # ------------------------------------------------------------------ 2. band test

@@ -123,6 +123,14 @@ def _span_cases():
         "nnz = S - 1": [S - 11, 10],
         "nnz = S + 1": [S - 10, 11],
         "one rating": [1],
+        # empty rows: equal row_ptr entries under the binary search, and the row walk's
+        # `while (ee >= next ...)` stepping over more than one row (X rows are scaled apart
+        # below, so a mis-stepped row shows in reg)
+        "three empty rows first": [0, 0, 0] + light + [S, 4],
+        "empty rows on a group and on a span boundary": [S // 16, 0, 0, 5, S - S // 16 - 5,
+                                                         0, 0, 0, 7],
+        "empty rows last": [5, S - 5, 9, 0, 0],
+        "S - 1, two empty rows, 1": [S - 1, 0, 0, 1],
     }
 
 
@@ -138,6 +146,8 @@ def _check_span_cases(cases, rank, implicit, alpha):
         vals = rng.integers(-2, 11, len(rows)).astype(np.float32) / 2
         X = rng.normal(0, 0.5, (n_r, rank)).astype(np.float32)
         Y = rng.normal(0, 0.5, (n_c, rank)).astype(np.float32)
+        if 0 in lens:                      # row j scaled by 1 + j: every |x_j|^2 its own size
+            X *= (1 + np.arange(n_r, dtype=np.float32))[:, None]
         Xd, Yd = _table(X), _table(Y)
         got = {}
         # the side whose rows are `rows`, then the transposed side (rows = cols)
@@ -181,6 +191,47 @@ def test_more_than_256_partial_blocks(implicit):
     lens.append(257 * S + 1 - sum(lens))
     assert lens[-1] > 0 and sum(lens) == 257 * S + 1
     _check_span_cases({"nnz = 257 S + 1": lens}, 8, implicit, 40.0 if implicit else 1.0)
+
+
+@pytest.mark.parametrize("rank,implicit,alpha", [(17, False, 1.0), (128, True, 40.0)])
+def test_out_of_range_columns_add_no_data_term(rank, implicit, alpha):
+    """col = -1, n_cols and INT32_MAX at 5 % of the ratings: no data term and no read of Y
+    (include/als_hip.h), while the rating still counts in n, n_positive and reg: the kernel
+    counts before the range test.  Only the side whose columns they are can hold them (a CSR
+    has no row outside its range)."""
+    S = E.objective_span()
+    rng = np.random.default_rng(rank)
+    lens = rng.integers(1, 90, 40)
+    lens[7] = S + 11
+    rows = _lens_to_rows(lens)
+    n_r, n_c = len(lens), 29
+    cols = rng.integers(0, n_c, len(rows))
+    hit = rng.random(len(rows))
+    bad = hit < 0.05
+    cols[bad] = np.array([-1, n_c, 2 ** 31 - 1])[rng.integers(0, 3, int(bad.sum()))]
+    cols[:3] = (-1, n_c, 2 ** 31 - 1)               # a group's first gathers
+    cols[-1] = 2 ** 31 - 1
+    vals = rng.integers(-2, 11, len(rows)).astype(np.float32) / 2
+    X = rng.normal(0, 0.5, (n_r, rank)).astype(np.float32)
+    X *= (1 + np.arange(n_r, dtype=np.float32))[:, None]
+    Y = rng.normal(0, 0.5, (n_c, rank)).astype(np.float32)
+    ptr, c, v = R.csr(rows, cols, vals, n_r)
+    blk = types.SimpleNamespace(row_ptr=_dev(ptr, torch.int64), col=_dev(c, torch.int32),
+                                val=_dev(v, torch.float32), nnz=len(v), n_rows=n_r)
+    ws = _ws()
+    out = E.objective_side(blk, _table(X), _table(Y), n_c, rank, implicit, alpha, ws).tolist()
+    want = R.side(rows, cols, vals, X, Y, implicit, alpha, n_cols=n_c)
+    ok = (cols >= 0) & (cols < n_c)
+    dropped = R.side(rows[ok], cols[ok], vals[ok], X, Y, implicit, alpha)
+    kept = R.side(rows, np.where(ok, cols, 0), vals, X, Y, implicit, alpha)
+    assert want[:2] == dropped[:2] and want[2:] == kept[2:] and want[3] > dropped[3]
+    tol = 1e-12 * (want[1] + want[2])
+    print(f"K10 out-of-range cols k={rank}: got {out} want {want} tol {tol:.3e}")
+    assert out[3:] == want[3:]                      # n, n_positive: every rating
+    for g, w_ in zip(out[:3], want[:3]):            # data, scale: without them; reg: with
+        assert abs(g - w_) <= tol, (out, want)
+    assert abs(out[2] - dropped[2]) > 1e3 * tol     # reg without them is another number
+    assert E.objective_side(blk, _table(X), _table(Y), n_c, rank, implicit, alpha, ws).tolist() == out
 
 
 # ------------------------------------------------------------------ Gram kernel alone

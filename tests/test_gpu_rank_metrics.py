@@ -36,13 +36,14 @@ N_QS = (0, 1, 3, 4, 5, 257, 1030)
 RTOL = 1e-12
 
 
-@functools.lru_cache(maxsize=None)
-def pattern(at):
-    """(lists int32 [N_MAX, at], begin, end int64 [N_MAX], col int32, rows, per-row ref)."""
+def pattern_inputs(at, n_max=N_MAX):
+    """(lists int32 [n_max, at], begin, end int64 [n_max], col int32, rows): the pattern's
+    first n_max rows.  Rows are drawn one after another from one generator, so a shorter
+    pattern is a prefix of a longer one."""
     rng = np.random.default_rng(1000 + at)
-    lists = np.empty((N_MAX, at), np.int32)
-    begin = np.zeros(N_MAX, np.int64)
-    end = np.zeros(N_MAX, np.int64)
+    lists = np.empty((n_max, at), np.int32)
+    begin = np.zeros(n_max, np.int64)
+    end = np.zeros(n_max, np.int64)
     cols, off, labels = [], 0, []
 
     def new_range(lab):
@@ -52,7 +53,7 @@ def pattern(at):
         off += len(lab)
         return off - len(lab), off
 
-    for r in range(N_MAX):
+    for r in range(n_max):
         kind = r if r < 5 else r % 8
         rnd = rng.integers(0, N_V, at)
         if kind == 0:
@@ -88,7 +89,14 @@ def pattern(at):
         else:
             begin[r], end[r] = new_range(lab)
     col = np.concatenate(cols + [np.zeros(1, np.int32)])
-    rows = [(lists[r], labels[r]) for r in range(N_MAX)]
+    rows = [(lists[r], labels[r]) for r in range(n_max)]
+    return lists, begin, end, col, rows
+
+
+@functools.lru_cache(maxsize=None)
+def pattern(at):
+    """pattern_inputs(at) and the per-row reference of its N_MAX rows."""
+    lists, begin, end, col, rows = pattern_inputs(at)
     return lists, begin, end, col, rows, R.per_row(rows, at)
 
 
