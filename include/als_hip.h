@@ -791,6 +791,55 @@ int als_baseline_predict(const int32_t* urow, const int32_t* irow, int64_t n,
                          const double* bi, int32_t n_items, float* pred, uint8_t* known,
                          void* stream);
 
+/* ---- K17: add ratings to a built CSR side (the reference appends a new user's ratings to
+ *      the training set and fits again, RecommenderSystem.py:207-247; Spark rebuilds its
+ *      blocks from the union) -------------------------------------------------------------- */
+
+/* Added under ABI 9 without a version bump: two new symbols only, nothing existing changes.
+ * The CSR als_csr_build would make of concat(old ratings, batch), from the CSR of the
+ * old ratings and the CSR of the batch, in one streaming pass with no sort.  K1's layout makes
+ * that exact: dense rows are in ascending id order and a row keeps its ratings in input order,
+ * duplicates included, so every row of the result is its old segment followed by its batch
+ * segment.
+ *   old side    row_ptr_old int64 [n_old + 1], col_old int32 [nnz_old], val_old f32 [nnz_old],
+ *               nnz_old = row_ptr_old[n_old]; columns are dense rows of the other side as it
+ *               was, n_cols_old of them
+ *   new_of_old_row  int32 [n_old]: the dense row each old row has in the grown id map,
+ *               STRICTLY increasing, values in [0, n_new).  NULL = identity: no new row ids,
+ *               so n_new == n_old (or n_old == 0)
+ *   new_of_old_col  int32 [n_cols_old]: the same for the other side; NULL = identity
+ *   batch       row_ptr_add int64 [n_new + 1], col_add int32 [nnz_add], val_add f32 [nnz_add],
+ *               nnz_add = row_ptr_add[n_new]: als_csr_build of the batch alone against the
+ *               GROWN id maps, so rows and columns are already in the new dense spaces
+ *   outputs     row_ptr_out int64 [n_new + 1], col_out int32 [nnz_old + nnz_add],
+ *               val_out f32 [nnz_old + nnz_add]; they may not alias an input
+ * For every new row r with j = the number of old rows placed before r:
+ *   row_ptr_out[r] = row_ptr_old[j] + row_ptr_add[r]      (a lower bound in new_of_old_row
+ *                                                          per row: no scan)
+ *   the row holds the old segment of r (if new_of_old_row[j] == r), columns passed through
+ *   new_of_old_col, in its old order, then col_add / val_add of [row_ptr_add[r],
+ *   row_ptr_add[r + 1]).  Values are copied as bits.
+ * Work is split over output ENTRIES, als_csr_merge_tile() of them per workgroup whichever rows
+ * they fall in (one binary search in row_ptr_out per tile, then the rows in order), so an
+ * item row of 10^5 ratings costs per rating what a short one does.  Integer and copy work
+ * only, no atomics, every output word written once: two calls give identical bytes, and the
+ * result equals als_csr_build on the concatenation bit for bit.  No scratch is used.  An
+ * index that inconsistent row pointers would take outside col_old / col_add is not
+ * dereferenced (the entry is written as col -1, val 0), and an old column outside
+ * [0, n_cols_old) maps to -1.
+ * Checked on the host before any launch: a negative size, n_new < n_old, n_new > n_old > 0
+ * without new_of_old_row and null pointers (col / val of a side only when that side has
+ * entries) are ALS_EINVAL; n_new >= 2^31 - 1 or
+ * nnz_old + nnz_add >= 2^31 (K1's limit) ALS_EUNSUPPORTED.  nnz_add == 0 with NULL maps is a
+ * plain copy.  Cost beside als_csr_build and beside the byte floor: DESIGN.md section K17. */
+int32_t als_csr_merge_tile(void);
+int als_csr_merge(const int64_t* row_ptr_old, const int32_t* col_old, const float* val_old,
+                  int64_t nnz_old, int32_t n_old, int32_t n_cols_old,
+                  const int32_t* new_of_old_row, const int32_t* new_of_old_col,
+                  const int64_t* row_ptr_add, const int32_t* col_add, const float* val_add,
+                  int64_t nnz_add, int32_t n_new,
+                  int64_t* row_ptr_out, int32_t* col_out, float* val_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

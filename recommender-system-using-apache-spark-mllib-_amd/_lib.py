@@ -114,6 +114,8 @@ SIGNATURES = {
     "als_row_moments": (ctypes.c_int, [P, P, P, I64, I32, I32, P, P, P, P, P, SZ, P]),
     "als_bias_update": (ctypes.c_int, [P, I32, P, P, P]),
     "als_baseline_predict": (ctypes.c_int, [P, P, I64, P, P, I32, P, I32, P, P, P]),
+    "als_csr_merge_tile": (I32, []),
+    "als_csr_merge": (ctypes.c_int, [P, P, P, I64, I32, I32, P, P, P, P, P, I64, I32, P, P, P, P]),
 }
 
 ABI_VERSION = 9

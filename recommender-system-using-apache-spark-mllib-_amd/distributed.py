@@ -50,7 +50,7 @@ from .filters import (reject_sharded_diversify, reject_sharded_explain, reject_s
                       reject_sharded_nonnegative,
                       reject_sharded_objective, reject_sharded_rating_stats,
                       reject_sharded_regression,
-                      reject_sharded_similar)
+                      reject_sharded_similar, reject_sharded_update)
 
 
 class HipKernels:
@@ -1015,6 +1015,18 @@ class ShardedALS:
                      sweeps: int = 10):
         """ALSCore.fit_baseline is not offered on the sharded engine yet."""
         reject_sharded_rating_stats()
+
+    def add_ratings(self, users, items, ratings, *, seed=0) -> dict:
+        """ALSCore.add_ratings is not offered on the sharded engine yet."""
+        reject_sharded_update()
+
+    def refresh(self, *, reg=None, implicit=None, alpha=None, nonnegative=None, sweeps=1):
+        """ALSCore.refresh is not offered on the sharded engine yet."""
+        reject_sharded_update()
+
+    def refit(self, max_iter, **fit_kwargs):
+        """ALSCore.refit is not offered on the sharded engine yet."""
+        reject_sharded_update()
 
     def regression_metrics(self, users, items, ratings, through_origin: bool = False) -> dict:
         """ALSCore.regression_metrics is not offered on the sharded engine yet."""

@@ -200,9 +200,10 @@ class RatingBlock:
         return self.short_nnz[d] if (d and self.short_nnz) else 0
 
 
-def build_block(row_ids: torch.Tensor, row_index: IdIndex, col_ids: torch.Tensor,
-                col_index: IdIndex, vals: torch.Tensor, ws: Workspace,
-                chunk: int = DEFAULT_CHUNK) -> RatingBlock:
+def build_csr(row_ids: torch.Tensor, row_index: IdIndex, col_ids: torch.Tensor,
+              col_index: IdIndex, vals: torch.Tensor, ws: Workspace):
+    """K1 (als_csr_build) alone: (row_ptr int64 [n + 1], col int32, val f32) of one side,
+    without a schedule."""
     L = _lib.lib()
     dev = row_ids.device
     nnz = int(row_ids.numel())
@@ -214,7 +215,76 @@ def build_block(row_ids: torch.Tensor, row_index: IdIndex, col_ids: torch.Tensor
     check(L.als_csr_build(ptr(row_ids), ptr(row_index.map), ptr(col_ids), ptr(col_index.map),
                           ptr(vals), nnz, n_rows, ptr(row_ptr), ptr(col), ptr(val), ptr(w),
                           w.numel(), stream_ptr(dev)), "als_csr_build")
-    return schedule_block(n_rows, nnz, row_ptr, col, val, ws, chunk)
+    return row_ptr, col, val
+
+
+def build_block(row_ids: torch.Tensor, row_index: IdIndex, col_ids: torch.Tensor,
+                col_index: IdIndex, vals: torch.Tensor, ws: Workspace,
+                chunk: int = DEFAULT_CHUNK) -> RatingBlock:
+    row_ptr, col, val = build_csr(row_ids, row_index, col_ids, col_index, vals, ws)
+    return schedule_block(row_index.n, int(row_ids.numel()), row_ptr, col, val, ws, chunk)
+
+
+def csr_merge_tile() -> int:
+    """Output entries per workgroup of als_csr_merge (tests size their shapes from it)."""
+    return int(_lib.lib().als_csr_merge_tile())
+
+
+def merge_csr(row_ptr_old, col_old, val_old, n_cols_old: int, row_map, col_map, row_ptr_add,
+              col_add, val_add):
+    """K17 (als_csr_merge): the CSR K1 would build from concat(old ratings, batch), from the
+    old side's CSR and the batch's CSR (built by K1 against the grown id maps), in one pass
+    with no sort.  row_map / col_map: int32 [n_old] / [n_cols_old], the dense row each old
+    row of this / the other side has after the growth, None where the side gained no id.
+    Returns (row_ptr int64 [n_new + 1], col int32, val f32); the contract is in
+    include/als_hip.h."""
+    L = _lib.lib()
+    dev = row_ptr_old.device
+    n_old, n_new = int(row_ptr_old.numel()) - 1, int(row_ptr_add.numel()) - 1
+    nnz_old, nnz_add = int(col_old.numel()), int(col_add.numel())
+    row_ptr = torch.empty(n_new + 1, dtype=torch.int64, device=dev)
+    col = torch.empty(nnz_old + nnz_add, dtype=torch.int32, device=dev)
+    val = torch.empty(nnz_old + nnz_add, dtype=torch.float32, device=dev)
+    check(L.als_csr_merge(ptr(row_ptr_old), ptr(col_old), ptr(val_old), nnz_old, n_old,
+                          int(n_cols_old), ptr(row_map), ptr(col_map), ptr(row_ptr_add),
+                          ptr(col_add), ptr(val_add), nnz_add, n_new, ptr(row_ptr), ptr(col),
+                          ptr(val), stream_ptr(dev)), "als_csr_merge")
+    return row_ptr, col, val
+
+
+def grow_index(index: IdIndex, ids: torch.Tensor, ws: Workspace):
+    """The id map of `index`'s ids plus `ids` (int32 original ids, device), as a fresh
+    build_index over the union would make it: (grown IdIndex, new_of_old, new_rows).
+    new_of_old: int32 [index.n], the dense row each old row has now (strictly increasing),
+    None when no id is new; new_rows: int64, the dense rows of the new ids, ascending.  A new
+    id below the old offset, or a negative one, re-bases the map (id_offset of the union)."""
+    dev = ids.device
+    old_lo, old_hi = int(index.uniq[0]) + index.offset, int(index.uniq[-1]) + index.offset
+    lo, hi = min(old_lo, int(ids.min())), max(old_hi, int(ids.max()))
+    off = id_offset(lo, hi)
+    old_keys = (index.uniq.long() + (index.offset - off))
+    keys = torch.cat([old_keys, ids.long() - off]).to(torch.int32).contiguous()
+    grown = build_index(keys, hi - off + 1, ws)
+    grown.offset = off
+    if grown.n == index.n:
+        return grown, None, torch.empty(0, dtype=torch.int64, device=dev)
+    new_of_old = grown.map[old_keys].contiguous()
+    is_new = torch.ones(grown.n, dtype=torch.bool, device=dev)
+    is_new[new_of_old.long()] = False
+    return grown, new_of_old, is_new.nonzero().flatten()
+
+
+def gather_rows(row_ptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, rows: torch.Tensor):
+    """The ragged rows `rows` (int64 dense rows) of a CSR as a CSR of their own, each row's
+    entries in its stored order: (row_ptr int64 [m + 1], col int32, val f32), the input of
+    fold_in_rows / nnls_rows."""
+    beg = row_ptr[rows]
+    ln = row_ptr[rows + 1] - beg
+    out_ptr = torch.zeros(rows.numel() + 1, dtype=torch.int64, device=row_ptr.device)
+    out_ptr[1:] = torch.cumsum(ln, 0)
+    src = torch.repeat_interleave(beg - out_ptr[:-1], ln) + torch.arange(
+        int(out_ptr[-1]), device=row_ptr.device)
+    return out_ptr, col[src].contiguous(), val[src].contiguous()
 
 
 def schedule_block(n_rows, nnz, row_ptr, col, val, ws: Workspace, chunk: int = DEFAULT_CHUNK
@@ -1323,6 +1393,8 @@ class ALSCore:
         self.item_block = build_block(i, self.iidx, u, self.uidx, r, self.ws, chunk)
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._train_ex = {}  # user_side -> sorted training exclusion list (train_exclusion)
+        self._fit_params = None  # reg / implicit / alpha / nonnegative of the last fit
+        self._touched = None     # (user rows, item rows) that took ratings since the last fit
         self.objective_history = []   # (iteration, objective) pairs of the last fit (K10)
         self.iterations_run = 0       # where the last fit stopped
         self.U: Optional[torch.Tensor] = None
@@ -1343,6 +1415,8 @@ class ALSCore:
         self._auto_chunk = False
         self.user_block = self.item_block = None
         self._train_ex = {}
+        self._fit_params = None
+        self._touched = None
         self.objective_history = []
         self.iterations_run = 0
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -1530,6 +1604,9 @@ class ALSCore:
         if Vc is not None:
             self.V[:, :rank] = _to_device(Vc, torch.float32, self.device)
         self.status.zero_()
+        self._fit_params = {"reg": float(reg), "implicit": bool(implicit), "alpha": float(alpha),
+                            "nonnegative": nonnegative}
+        self._touched = None   # a fit re-solves every row
         self.objective_history = []
         self.iterations_run = start
         prev = None
@@ -1551,6 +1628,214 @@ class ALSCore:
                 break
         self.check_status()
         return self
+
+    # ---- K17: ratings that arrive after the fit ----
+    def _solve_rows(self, csr, rows, Y, n_src, p, yty_of=None):
+        """(X f32 [m, ld], n_used int32 [m]) of the dense rows `rows` of the CSR (row_ptr,
+        col, val), each from its full rating list in stored order against the fixed factors
+        Y: K7, or K13 when the fit was nonnegative.  yty_of: (table, rows) the implicit YtY
+        is taken of, None = Y.  Raises, before anything is stored, for a row that is not
+        positive definite."""
+        row_ptr, col, val = gather_rows(*csr, rows)
+        yty = compute_yty(*(yty_of or (Y, n_src)), self.rank, self.ws_yty) if p["implicit"] else None
+        if p["nonnegative"]:
+            if getattr(self, "ws_nnls", None) is None:
+                self.ws_nnls = Workspace(self.device)
+            X, n_used, _ = nnls_rows(row_ptr, col, val, Y, n_src, self.rank, p["reg"],
+                                     p["implicit"], p["alpha"], yty, self.ws_nnls)
+            return X, n_used
+        if getattr(self, "ws_rows", None) is None:
+            # a buffer of its own: the solve workspace keeps its rating scale word
+            self.ws_rows = Workspace(self.device)
+        status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        X, n_used = fold_in_rows(row_ptr, col, val, Y, n_src, self.rank, p["reg"], p["implicit"],
+                                 p["alpha"], yty, status, self.ws_rows)
+        raise_status(int(status.item()), " of the rows being re-solved (ascending dense row)")
+        return X, n_used
+
+    def _update_params(self, reg=None, implicit=None, alpha=None, nonnegative=None) -> dict:
+        p = dict(self._fit_params or {})
+        for k, v in (("reg", reg), ("implicit", implicit), ("alpha", alpha),
+                     ("nonnegative", nonnegative)):
+            if v is not None:
+                p[k] = v
+        if "reg" not in p:
+            raise ValueError("no fit to take reg / implicit / alpha / nonnegative from: fit() "
+                             "the core first, or pass reg=")
+        p = {"reg": float(p["reg"]), "implicit": bool(p.get("implicit", False)),
+             "alpha": float(p.get("alpha", 1.0)), "nonnegative": bool(p.get("nonnegative", False))}
+        if p["reg"] < 0 or p["alpha"] < 0:
+            raise ValueError(f"reg and alpha must be >= 0, got {p['reg']}, {p['alpha']}")
+        return p
+
+    def add_ratings(self, users, items, ratings, *, seed=0) -> dict:
+        """Add a batch of ratings to the core in place (the reference adds a new user's
+        twelve ratings to the training set and fits again, RecommenderSystem.py:207-247).
+        users / items / ratings: host or device arrays of one length; new ids on either side
+        are welcome, and a pair that is already rated (or twice in the batch) is one more
+        rating, as Spark keeps duplicates.  After the call every rating-derived thing — both
+        id maps, both CSR sides and their schedules, nnz — is what ALSCore(concat(old,
+        batch)) would hold, bit for bit:
+          a. both id maps grow (als_index_build over the old ids plus the batch's; a new id
+             below the offset, or a negative one, re-bases the map)
+          b. K1 builds the batch's two small CSRs against the grown maps
+          c. K17 (als_csr_merge) writes each side's merged CSR in one pass with no sort, and
+             the side is scheduled again at its current chunk
+          d. on a core with factors, the rows of U and V move to their new places bit for
+             bit and every NEW row gets factors: new users from their ratings against the
+             current V (K7, or K13 after a nonnegative fit; the parameters of the last fit;
+             a rating of an item that is new as well is left out, as fold_in leaves out an
+             unknown item), then new items against the grown U.  A new row without a used
+             rating — a new user who rated only new items — gets a unit-norm Gaussian row
+             from `seed`, as init_factors gives: a zero row would stay zero through every
+             later sweep.  Rows that existed keep their factors until refresh() or refit()
+          e. everything cached from the ratings (the train exclusion lists, the workspace's
+             rating scale) is dropped.
+        Needs one transient second copy of each side's col and val (8 B per rating and
+        side, until the call returns).  An empty batch is a no-op; before any fit only the ratings are
+        merged.  Nothing is changed when the call raises.
+        Returns {"added", "new_users", "new_items" (ids, ascending), "touched_users",
+        "touched_items" (int64 dense rows in the grown maps, ascending: the rows whose
+        rating lists changed)}; the touched rows of every add since the last fit are kept
+        for refresh()."""
+        if self.user_block is None:
+            raise ValueError("add_ratings needs the ratings the model was fitted on; this core "
+                             "was built from saved factors (from_factors / load) and has none")
+        u = _to_device(users, torch.int32, self.device)
+        i = _to_device(items, torch.int32, self.device)
+        r = _to_device(ratings, torch.float32, self.device)
+        if not (u.numel() == i.numel() == r.numel()):
+            raise ValueError("users, items and ratings must have the same length")
+        empty = torch.empty(0, dtype=torch.int64, device=self.device)
+        if u.numel() == 0:
+            return {"added": 0, "new_users": empty.to(torch.int32), "new_items":
+                    empty.to(torch.int32), "touched_users": empty, "touched_items": empty}
+        uidx, umap, new_u = grow_index(self.uidx, u, self.ws)
+        iidx, imap, new_i = grow_index(self.iidx, i, self.ws)
+        uk, ik = uidx.keys(u), iidx.keys(i)
+        ub, ib = self.user_block, self.item_block
+        add_u = build_csr(uk, uidx, ik, iidx, r, self.ws)
+        user_csr = merge_csr(ub.row_ptr, ub.col, ub.val, ib.n_rows, umap, imap, *add_u)
+        add_i = build_csr(ik, iidx, uk, uidx, r, self.ws)
+        item_csr = merge_csr(ib.row_ptr, ib.col, ib.val, ub.n_rows, imap, umap, *add_i)
+        nnz = self.nnz + int(u.numel())
+        touched_u = (add_u[0][1:] > add_u[0][:-1]).nonzero().flatten()
+        touched_i = (add_i[0][1:] > add_i[0][:-1]).nonzero().flatten()
+        U = V = None
+        if self.rank > 0 and self.U is not None:
+            U, V = self._grown_factors(uidx.n, iidx.n, umap, imap, new_u, new_i, user_csr,
+                                       item_csr, int(seed))
+        # nothing above touched the core: from here on it cannot fail half-way
+        self.user_block = schedule_block(uidx.n, nnz, *user_csr, self.ws, ub.chunk)
+        self.item_block = schedule_block(iidx.n, nnz, *item_csr, self.ws, ib.chunk)
+        self.uidx, self.iidx, self.nnz = uidx, iidx, nnz
+        if U is not None:
+            self.U, self.V = U, V
+        self._train_ex = {}
+        self.ws.rating_scale_key = None   # the batch may hold the largest |rating|
+        if self._touched is not None:    # rows touched earlier, in the grown numbering
+            tu, ti = self._touched
+            tu = tu if umap is None else umap[tu].long()
+            ti = ti if imap is None else imap[ti].long()
+            touched_all = (torch.unique(torch.cat([tu, touched_u])),
+                           torch.unique(torch.cat([ti, touched_i])))
+        else:
+            touched_all = (touched_u, touched_i)
+        self._touched = touched_all
+        return {"added": int(u.numel()), "new_users": uidx.ids()[new_u], "new_items":
+                iidx.ids()[new_i], "touched_users": touched_u, "touched_items": touched_i}
+
+    def _grown_factors(self, n_u, n_i, umap, imap, new_u, new_i, user_csr, item_csr, seed):
+        """add_ratings step d: (U, V) for the grown id maps."""
+        ld = ld_for(self.rank)
+
+        def moved(F, n, mp):
+            if mp is None:
+                return F.clone()
+            out = torch.zeros((n, ld), dtype=torch.float32, device=self.device)
+            out[mp.long()] = F
+            return out
+
+        U, V = moved(self.U, n_u, umap), moved(self.V, n_i, imap)
+        p = self._update_params() if self._fit_params else None
+        g = torch.Generator(device=self.device)
+        g.manual_seed(int(seed) & 0x7FFFFFFFFFFFFFFF)
+
+        def fill(F, rows, csr, Y, n_src, unknown_cols, yty_of=None):
+            if rows.numel() == 0:
+                return
+            X = torch.zeros((rows.numel(), ld), dtype=torch.float32, device=self.device)
+            n_used = torch.zeros(rows.numel(), dtype=torch.int32, device=self.device)
+            if p is not None:
+                row_ptr, col, val = csr
+                if unknown_cols.numel():   # a column that has no factors yet is not used
+                    hide = torch.zeros(n_src, dtype=torch.bool, device=self.device)
+                    hide[unknown_cols] = True
+                    col = torch.where(hide[col.long()], -1, col).to(torch.int32)
+                X, n_used = self._solve_rows((row_ptr, col, val), rows, Y, n_src, p, yty_of)
+            blank = (n_used == 0).nonzero().flatten()
+            if blank.numel():
+                x = torch.randn((blank.numel(), self.rank), generator=g, device=self.device,
+                                dtype=torch.float32)
+                X[blank] = 0
+                X[blank, :self.rank] = x / torch.linalg.vector_norm(x, dim=1, keepdim=True)
+            F[rows] = X
+
+        # YtY of the V the model had: the rows just added are zero and add nothing, and the
+        # sum keeps the bits fold_in would have used before the growth
+        fill(U, new_u, user_csr, V, n_i, new_i, (self.V, self.n_items))
+        fill(V, new_i, item_csr, U, n_u, new_u[:0])
+        return U, V
+
+    def refresh(self, *, reg=None, implicit=None, alpha=None, nonnegative=None, sweeps=1):
+        """Re-solve only the rows add_ratings touched since the last fit — the "serve it
+        now" path between add_ratings and the next refit: touched users against V, then
+        touched items against the new U, `sweeps` times, each row from its full merged rating
+        list in block order (K7 als_fold_in, or K13 als_nnls_rows when nonnegative; YtY of
+        the fixed side when implicit).  Every other row keeps its bits.  reg / implicit /
+        alpha / nonnegative default to those of the last fit.  One workgroup per row in
+        fp64, so it pays for a handful of rows only: on the ML-25M shape at rank 64 one new
+        user's 12 ratings (1 + 12 rows) take 1.0 ms, 0.6 of a full iteration, but a batch of
+        10^4 ratings (19 thousand rows) 12.6 ms, 7.5 iterations — there refit(1) is the
+        cheaper call.  Returns self."""
+        if self.user_block is None:
+            raise ValueError("refresh needs the ratings the model was fitted on; this core "
+                             "was built from saved factors (from_factors / load) and has none")
+        if self.U is None or self.V is None:
+            raise ValueError("refresh needs factors: fit() the core first")
+        p = self._update_params(reg, implicit, alpha, nonnegative)
+        if int(sweeps) < 1:
+            raise ValueError(f"sweeps must be >= 1, got {sweeps}")
+        if self._touched is None:
+            return self
+        tu, ti = self._touched
+        for _ in range(int(sweeps)):
+            if tu.numel():
+                b = self.user_block
+                X, _ = self._solve_rows((b.row_ptr, b.col, b.val), tu, self.V, self.n_items, p)
+                self.U[tu] = X
+            if ti.numel():
+                b = self.item_block
+                X, _ = self._solve_rows((b.row_ptr, b.col, b.val), ti, self.U, self.n_users, p)
+                self.V[ti] = X
+        return self
+
+    def refit(self, max_iter, **fit_kwargs):
+        """The warm start: fit(rank, max_iter, ..., U0=the current U) with the parameters of
+        the last fit (fit_kwargs override them and pass objective_every / tol through).
+        Spark's order solves the items first from U alone and never reads V, so continuing
+        from the current U is continuing the fit."""
+        if self.user_block is None:
+            raise ValueError("refit needs the ratings the model was fitted on; this core "
+                             "was built from saved factors (from_factors / load) and has none")
+        if self.U is None or self.rank < 1:
+            raise ValueError("refit needs factors: fit() the core first")
+        if "U0" in fit_kwargs or "rank" in fit_kwargs:
+            raise ValueError("refit starts from the current U at the current rank")
+        kw = self._update_params(*(fit_kwargs.pop(k, None) for k in
+                                   ("reg", "implicit", "alpha", "nonnegative")))
+        kw.update(fit_kwargs)
+        return self.fit(self.rank, int(max_iter), U0=self.U[:, :self.rank].clone(), **kw)
 
     def fingerprint(self) -> dict:
         """Order-independent identity of the training ratings (checkpoint matching)."""

@@ -178,6 +178,14 @@ def reject_sharded_list_metrics() -> None:
         "with popularity=)")
 
 
+def reject_sharded_update() -> None:
+    """The sharded engine carries add_ratings / refresh / refit with the single-GPU
+    signature and refuses them."""
+    raise NotImplementedError(
+        "add_ratings / refresh / refit are not supported by the sharded engine (ShardedALS) "
+        "yet: ratings are added in place on the single-GPU engine, an ALSCore")
+
+
 def reject_sharded_rating_stats() -> None:
     """The sharded engine carries rating_stats / global_stats / top_rated / fit_baseline with
     the single-GPU signature and refuses them, as it refuses list_metrics."""

@@ -222,7 +222,10 @@ class ALS(_Params):
             return self.copy(params).fit(dataset)
         _validate(self._p)
         core = _engine.make_engine(*self._columns(dataset))
-        return ALSModel(self._fit_core(core), dict(self._p), solver=self._solver)
+        model = ALSModel(self._fit_core(core), dict(self._p), solver=self._solver)
+        # ALSModel.update's refit records the objective as this fit did
+        model._objective_every = self._objective_every or int(self._objective_tol is not None)
+        return model
 
 
 _make_accessors(ALS, list(_Params._defaults))
@@ -240,6 +243,7 @@ class ALSModel:
         self._solver = solver
         # the fit's (iteration, objective) pairs, copied: a tuner refits the same core
         self._objective_history = list(getattr(core, "objective_history", ()))
+        self._objective_every = 0   # ALS.fit sets it from setObjectiveHistory
 
     # -- params used at transform time --
     def setUserCol(self, v):
@@ -302,6 +306,35 @@ class ALSModel:
         p = self._p
         return self._core.objective(float(p["regParam"]), bool(p["implicitPrefs"]),
                                     float(p["alpha"]))
+
+    def update(self, dataset, maxIter: int = 2, mode: str = "refit") -> "ALSModel":
+        """Add the ratings of `dataset` (this model's userCol / itemCol / ratingCol) to the
+        model's training data and bring the factors up to date, without building the model
+        again (K17, ALSCore.add_ratings).  THIS MODEL IS CHANGED IN PLACE and returned; new
+        users and items become rows of userFactors / itemFactors.
+        mode: "refit"   maxIter warm iterations over all rows from the current user factors,
+                        with the regParam / implicitPrefs / alpha / solver of the fit;
+                        objectiveHistory then holds the refit's values when the estimator
+                        had setObjectiveHistory on
+              "refresh" only the users and items of `dataset` are solved again, everyone
+                        else keeps their factors (ALSCore.refresh)
+              "none"    the ratings are merged and new rows get fold-in factors; nothing
+                        else moves.
+        Not on a loaded model (no training data) nor on the sharded engine."""
+        if mode not in ("refit", "refresh", "none"):
+            raise ValueError(f"mode must be 'refit', 'refresh' or 'none', got {mode!r}")
+        p = self._p
+        u, i, r = columns_of(dataset, (p["userCol"], p["itemCol"], p["ratingCol"]))
+        seed = _DEFAULT_SEED if p["seed"] is None else int(p["seed"])
+        self._core.add_ratings(check_integers(u, p["userCol"]), check_integers(i, p["itemCol"]),
+                               to_float32(r), seed=seed)
+        if mode == "refit":
+            observe = {"objective_every": self._objective_every} if self._objective_every else {}
+            self._core.refit(int(maxIter), **observe)
+            self._objective_history = list(self._core.objective_history)
+        elif mode == "refresh":
+            self._core.refresh()
+        return self
 
     def _factors_df(self, ids, F):
         import pandas as pd

@@ -337,6 +337,28 @@ class MatrixFactorizationModel:
                   for a, b, c in zip(ids[r, :n[r]], rat[r, :n[r]], con[r, :n[r]])])
                 for r in range(len(uu))]
 
+    def update(self, ratings, iterations: int = 2, mode: str = "refit"
+               ) -> "MatrixFactorizationModel":
+        """Add `ratings` (tuples or Ratings, as ALS.train takes them) to the model's training
+        data and bring the factors up to date without training again — the reference's
+        "add my ratings, train again" (RecommenderSystem.py:207-218) on the model it already
+        has (K17, ALSCore.add_ratings).  THIS MODEL IS CHANGED IN PLACE and returned.
+        mode: "refit" = `iterations` warm iterations over all rows from the current user
+        features, with the lambda / implicit / alpha / solver it was trained with;
+        "refresh" = only the users and products of `ratings` are solved again; "none" = the
+        ratings are merged and new ids get fold-in features.  Not on a loaded model."""
+        if mode not in ("refit", "refresh", "none"):
+            raise ValueError(f"mode must be 'refit', 'refresh' or 'none', got {mode!r}")
+        if int(iterations) < 0:
+            raise ValueError(f"iterations must be >= 0, got {iterations}")
+        u, i, r = _triples(ratings)
+        self._core.add_ratings(u, i, r, seed=_DEFAULT_SEED)
+        if mode == "refit":
+            self._core.refit(int(iterations))
+        elif mode == "refresh":
+            self._core.refresh()
+        return self
+
     def save(self, sc, path: str, overwrite: bool = False) -> None:
         """MatrixFactorizationModel.save(sc, path) in Spark's layout (``sc`` is ignored)."""
         from .. import persistence

@@ -21,7 +21,8 @@ from typing import Dict, Iterable, List, Sequence, Tuple
 import numpy as np
 
 __all__ = ["movie_counts_and_averages", "highest_rated_movies", "personal_recommendations",
-           "personal_recommendations_fold_in", "personal_explanations", "similar_movies"]
+           "personal_recommendations_fold_in", "personal_recommendations_update",
+           "personal_explanations", "similar_movies"]
 
 
 def movie_counts_and_averages(ratings) -> Dict[int, Tuple[int, float]]:
@@ -189,6 +190,36 @@ def similar_movies(model, movie_ids: Iterable[int], movies: Iterable[Sequence], 
     name = lambda a: titles.get(int(a), str(int(a)))
     return [(name(k), [(name(a), float(s)) for a, s in zip(ri, rs) if np.isfinite(s)])
             for k, ri, rs in zip(keys, ids, sc)]
+
+
+def personal_recommendations_update(model, user_id: int, rated: Iterable[Sequence],
+                                    movies: Iterable[Sequence], num: int = 20,
+                                    min_ratings: int = 75, iterations: int = 2
+                                    ) -> List[Tuple[float, str, int]]:
+    """R:207-247 without building the model again: the user's ratings are added to the
+    model's own training data (K17, ALSCore.add_ratings), the model is refitted warm for
+    `iterations` iterations from its current user factors (ALSCore.refit), and the list is
+    personal_recommendations' — (predicted rating, movie name, number of ratings) of the
+    user's top `num` unrated movies with more than `min_ratings` ratings.  The counts are
+    the engine's own statistics (K16) after the merge, so the ratings just added count.
+    THE MODEL IS CHANGED IN PLACE: it now knows the user.
+
+    rated:  the user's (user, movie, rating) triples (myRatedMovies, R:190-202), all of
+            `user_id`
+    movies: (MovieID, title) pairs (moviesRDD, R:39)."""
+    rated = [(int(u), int(m), float(r)) for u, m, r, *_ in rated]
+    if any(u != int(user_id) for u, _, _ in rated):
+        raise ValueError("rated must hold the ratings of user_id")
+    eng = _engine_of(model)
+    if rated:
+        u, m, r = (np.asarray(x) for x in zip(*rated))
+        eng.add_ratings(u.astype(np.int32), m.astype(np.int32), r.astype(np.float32))
+        eng.refit(int(iterations))
+    stats = eng.rating_stats(user_side=False)
+    counts = dict(zip(stats["ids"].cpu().numpy().tolist(),
+                      stats["count"].cpu().numpy().astype(np.int64).tolist()))
+    return personal_recommendations(model, user_id, rated, movies, counts,
+                                    min_count=int(min_ratings), num=int(num))
 
 
 def personal_recommendations(model, user_id: int, rated: Iterable[Sequence],
