@@ -26,7 +26,8 @@ rows in the fp64 rescue list after the launches: a rescued row is the reference'
 arithmetic and would hide a broken fp32 tail (unit-norm factors at regParam 0.1 miss all
 three rescue tests: trace(G) / (lambda n) = 10, operands at the launch maximum, fp64
 pivot spreads <= 11 of 32 explicit and < 4 of 8 implicit, test_k2k3_edges_cpu.py).  The
-destination table is prefilled with 7.0: the
+rescue kernel itself is held to its own, fp64-grade bar on these same inputs in
+test_gpu_rescue64.py.  The destination table is prefilled with 7.0: the
 padding columns [rank, ld) must come back exactly 0 and no 7.0 may survive.
 """
 import numpy as np
