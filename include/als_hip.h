@@ -840,6 +840,72 @@ int als_csr_merge(const int64_t* row_ptr_old, const int32_t* col_old, const floa
                   int64_t nnz_add, int32_t n_new,
                   int64_t* row_ptr_out, int32_t* col_out, float* val_out, void* stream);
 
+/* ---- K18: remove ratings from a built CSR side (un-rate a pair, forget a user, withdraw an
+ *      item; Spark rebuilds its blocks from the filtered set) ------------------------------- */
+
+/* Added under ABI 9 without a version bump: four new symbols only, nothing existing changes.
+ * The CSR als_csr_build would make of the old ratings with every copy of every listed
+ * (row, column) pair filtered out and the order kept, from the CSR of the old ratings, as a
+ * stream compaction in two calls with no sort.  K1's layout makes that exact: dense rows are in
+ * ascending id order and a row keeps its ratings in input order, duplicates included, so every
+ * row of the result is the stored row with the listed entries dropped.
+ *   old side    row_ptr_old int64 [n_old + 1], col_old int32 [nnz_old], val_old f32 [nnz_old],
+ *               nnz_old = row_ptr_old[n_old]; rows may be empty
+ *   delete list a CSR over the same dense rows: row_ptr_del int64 [n_old + 1], col_del int32
+ *               [nnz_del], each row's columns ASCENDING (a column listed twice is harmless);
+ *               both may be NULL when nnz_del == 0
+ *   tiles       = ceil(nnz_old / als_csr_remove_tile()); the tile is a multiple of 64
+ * als_csr_remove_mark writes
+ *   keep_bits   uint64 [ceil(nnz_old / 64)]: bit q % 64 of word q / 64 is 1 iff entry q stays,
+ *               i.e. col_old[q] does not occur in its row's delete list (a binary search; a row
+ *               with an empty list costs one comparison).  Every stored copy of a listed pair
+ *               goes.  One wave ballot per word; the tail bits of the last word are 0
+ *   tile_off    int64 [tiles + 1]: the exclusive scan of the tiles' kept counts, so
+ *               tile_off[tiles] = nnz_out.  The counts go through `scratch` (int32 [tiles],
+ *               als_csr_remove_scratch_bytes(nnz_old, n_old) bytes) and are scanned by one
+ *               workgroup of the same call: no host read
+ *   row_ptr_kept int64 [n_old + 1], in the OLD row numbering: the number of kept entries before
+ *               row_ptr_old[r] (tile_off of its tile plus popcounts of that tile's words below
+ *               it), so row r keeps row_ptr_kept[r + 1] - row_ptr_kept[r] entries — 0 for a row
+ *               that lost everything or was empty — and row_ptr_kept[n_old] = nnz_out.  The row
+ *               pointer of the result is row_ptr_kept restricted to the rows the caller keeps
+ *   del_hits    int32 [nnz_del] or NULL: the stored copies dropped for each listed pair (0 = the
+ *               pair was not stored); zeroed and then counted with integer atomic adds, the only
+ *               atomics of K18
+ * als_csr_remove_compact takes col_old, val_old, keep_bits and tile_off as mark left them, and
+ *   new_of_old_col int32 [n_cols_old] or NULL: the dense row each old row of the OTHER side has
+ *               after its rows left, -1 for a row that left; NULL = identity (the column is
+ *               copied).  With a map, a column outside [0, n_cols_old) is written as -1
+ *   outputs     col_out int32 [nnz_out], val_out f32 [nnz_out], nnz_out = tile_off[tiles] read
+ *               by the caller (who needs row_ptr_kept on the host anyway to see which rows
+ *               left).  Kept entry q goes to tile_off[q / tile] + its rank among the tile's kept
+ *               entries; the value is copied as bits.  No output may alias an input
+ * Work is split over stored ENTRIES, one tile per workgroup whichever rows they fall in (one
+ * binary search in row_ptr_old per tile, then the rows in order through LDS), so an item row of
+ * 10^5 ratings costs per rating what a short one does.  No sort, no floating-point arithmetic,
+ * every output word written once (del_hits: zeroed, then added to): two calls give identical
+ * bytes, and row pointer, columns and values equal als_csr_build on the filtered ratings bit for
+ * bit.  An index that inconsistent row pointers or a foreign tile_off would take outside a buffer
+ * is not dereferenced (delete ranges are clamped to [0, nnz_del], row positions to [0, nnz_old],
+ * destinations outside [0, nnz_out) are skipped).
+ * Checked on the host before any launch: a negative size and a null pointer (col / val /
+ * keep_bits only when the side has entries, the delete list only when nnz_del > 0, outputs only
+ * when nnz_out > 0) are ALS_EINVAL, as is nnz_out > nnz_old; nnz_old >= 2^31 or
+ * n_old >= 2^31 - 1 (K1's limit) ALS_EUNSUPPORTED; a scratch below the stated size
+ * ALS_EWORKSPACE.  nnz_del == 0 is a plain copy: every bit set, row_ptr_kept == row_ptr_old.
+ * Cost beside als_csr_build and beside the byte floor: DESIGN.md section K18. */
+int32_t als_csr_remove_tile(void);
+size_t als_csr_remove_scratch_bytes(int64_t nnz_old, int32_t n_old);
+int als_csr_remove_mark(const int64_t* row_ptr_old, const int32_t* col_old, int64_t nnz_old,
+                        int32_t n_old, const int64_t* row_ptr_del, const int32_t* col_del,
+                        int64_t nnz_del, uint64_t* keep_bits, int64_t* tile_off,
+                        int64_t* row_ptr_kept, int32_t* del_hits, void* scratch,
+                        size_t scratch_bytes, void* stream);
+int als_csr_remove_compact(const int32_t* col_old, const float* val_old, int64_t nnz_old,
+                           const uint64_t* keep_bits, const int64_t* tile_off,
+                           const int32_t* new_of_old_col, int32_t n_cols_old, int32_t* col_out,
+                           float* val_out, int64_t nnz_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -116,6 +116,10 @@ SIGNATURES = {
     "als_baseline_predict": (ctypes.c_int, [P, P, I64, P, P, I32, P, I32, P, P, P]),
     "als_csr_merge_tile": (I32, []),
     "als_csr_merge": (ctypes.c_int, [P, P, P, I64, I32, I32, P, P, P, P, P, I64, I32, P, P, P, P]),
+    "als_csr_remove_tile": (I32, []),
+    "als_csr_remove_scratch_bytes": (SZ, [I64, I32]),
+    "als_csr_remove_mark": (ctypes.c_int, [P, P, I64, I32, P, P, I64, P, P, P, P, P, SZ, P]),
+    "als_csr_remove_compact": (ctypes.c_int, [P, P, I64, P, P, P, I32, P, P, I64, P]),
 }
 
 ABI_VERSION = 9

@@ -50,7 +50,7 @@ from .filters import (reject_sharded_diversify, reject_sharded_explain, reject_s
                       reject_sharded_nonnegative,
                       reject_sharded_objective, reject_sharded_rating_stats,
                       reject_sharded_regression,
-                      reject_sharded_similar, reject_sharded_update)
+                      reject_sharded_remove, reject_sharded_similar, reject_sharded_update)
 
 
 class HipKernels:
@@ -1027,6 +1027,22 @@ class ShardedALS:
     def refit(self, max_iter, **fit_kwargs):
         """ALSCore.refit is not offered on the sharded engine yet."""
         reject_sharded_update()
+
+    def remove_ratings(self, users, items) -> dict:
+        """ALSCore.remove_ratings is not offered on the sharded engine yet."""
+        reject_sharded_remove()
+
+    def remove_users(self, ids) -> dict:
+        """ALSCore.remove_users is not offered on the sharded engine yet."""
+        reject_sharded_remove()
+
+    def remove_items(self, ids) -> dict:
+        """ALSCore.remove_items is not offered on the sharded engine yet."""
+        reject_sharded_remove()
+
+    def set_ratings(self, users, items, ratings, *, seed=0) -> dict:
+        """ALSCore.set_ratings is not offered on the sharded engine yet."""
+        reject_sharded_remove()
 
     def regression_metrics(self, users, items, ratings, through_origin: bool = False) -> dict:
         """ALSCore.regression_metrics is not offered on the sharded engine yet."""

@@ -274,6 +274,83 @@ def grow_index(index: IdIndex, ids: torch.Tensor, ws: Workspace):
     return grown, new_of_old, is_new.nonzero().flatten()
 
 
+def csr_remove_tile() -> int:
+    """Stored entries per workgroup of K18 (tests size their shapes from it)."""
+    return int(_lib.lib().als_csr_remove_tile())
+
+
+def remove_mark(row_ptr_old, col_old, row_ptr_del, col_del, ws: Workspace, count_hits=False):
+    """K18, first call (als_csr_remove_mark): which stored entries of one side stay when the
+    pairs of the delete CSR (row_ptr_del int64 [n + 1], col_del int32, every row's columns
+    ascending; both None = delete nothing) leave.  Returns (keep_bits, tile_off, row_ptr_kept,
+    del_hits): one bit per stored entry (int64 words holding the uint64 bits), the exclusive
+    scan of the tiles' kept counts (tile_off[-1] = the entries that stay), the kept entries
+    before every old row, and with count_hits the stored copies dropped per listed pair
+    (else None).  The contract is in include/als_hip.h."""
+    L = _lib.lib()
+    dev = row_ptr_old.device
+    n_old, nnz_old = int(row_ptr_old.numel()) - 1, int(col_old.numel())
+    nnz_del = 0 if col_del is None else int(col_del.numel())
+    tiles = -(-nnz_old // csr_remove_tile())
+    keep_bits = torch.empty(-(-nnz_old // 64), dtype=torch.int64, device=dev)
+    tile_off = torch.empty(tiles + 1, dtype=torch.int64, device=dev)
+    row_ptr_kept = torch.empty(n_old + 1, dtype=torch.int64, device=dev)
+    hits = torch.empty(nnz_del, dtype=torch.int32, device=dev) if count_hits else None
+    w = ws.get(L.als_csr_remove_scratch_bytes(nnz_old, n_old))
+    check(L.als_csr_remove_mark(ptr(row_ptr_old), ptr(col_old), nnz_old, n_old, ptr(row_ptr_del),
+                                ptr(col_del), nnz_del, ptr(keep_bits), ptr(tile_off),
+                                ptr(row_ptr_kept), ptr(hits), ptr(w), w.numel(), stream_ptr(dev)),
+          "als_csr_remove_mark")
+    return keep_bits, tile_off, row_ptr_kept, hits
+
+
+def remove_compact(col_old, val_old, keep_bits, tile_off, col_map, n_cols_old: int,
+                   nnz_out: int):
+    """K18, second call (als_csr_remove_compact): (col int32 [nnz_out], val f32 [nnz_out]), the
+    kept entries in their stored order, columns passed through col_map (int32 [n_cols_old], the
+    dense row each old row of the other side has now, None = unchanged)."""
+    L = _lib.lib()
+    dev = col_old.device
+    col = torch.empty(int(nnz_out), dtype=torch.int32, device=dev)
+    val = torch.empty(int(nnz_out), dtype=torch.float32, device=dev)
+    check(L.als_csr_remove_compact(ptr(col_old), ptr(val_old), int(col_old.numel()),
+                                   ptr(keep_bits), ptr(tile_off), ptr(col_map), int(n_cols_old),
+                                   ptr(col), ptr(val), int(nnz_out), stream_ptr(dev)),
+          "als_csr_remove_compact")
+    return col, val
+
+
+def shrink_index(index: IdIndex, leaving_rows: torch.Tensor, ws: Workspace):
+    """The mirror of grow_index: the id map of `index` without the dense rows `leaving_rows`
+    (int64, device), as a fresh build_index over the remaining ids would make it — offset and
+    id_space are derived again, so they move when the smallest or the largest id leaves.
+    Returns (IdIndex, new_of_old): new_of_old int32 [index.n], the dense row each old row has
+    now, -1 for a row that left; (index, None) when none leaves.  At least one row must stay."""
+    if leaving_rows.numel() == 0:
+        return index, None
+    dev = index.uniq.device
+    stay = torch.ones(index.n, dtype=torch.bool, device=dev)
+    stay[leaving_rows] = False
+    ids = index.uniq[stay].long() + index.offset
+    if ids.numel() == 0:
+        raise ValueError("shrink_index: every row leaves")
+    lo, hi = int(ids[0]), int(ids[-1])
+    off = id_offset(lo, hi)
+    shrunk = build_index((ids - off).to(torch.int32).contiguous(), hi - off + 1, ws)
+    shrunk.offset = off
+    new_of_old = torch.full((index.n,), -1, dtype=torch.int32, device=dev)
+    new_of_old[stay] = torch.arange(shrunk.n, dtype=torch.int32, device=dev)
+    return shrunk, new_of_old
+
+
+def _delete_csr(rows: torch.Tensor, cols: torch.Tensor, n_rows: int):
+    """(row_ptr int64 [n_rows + 1], col int32) of distinct (row, col) pairs that are sorted by
+    row, then column: every row's columns ascending, as als_csr_remove_mark wants them."""
+    row_ptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=rows.device)
+    row_ptr[1:] = torch.cumsum(torch.bincount(rows, minlength=n_rows), 0)
+    return row_ptr, cols.to(torch.int32).contiguous()
+
+
 def gather_rows(row_ptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, rows: torch.Tensor):
     """The ragged rows `rows` (int64 dense rows) of a CSR as a CSR of their own, each row's
     entries in its stored order: (row_ptr int64 [m + 1], col int32, val f32), the input of
@@ -1710,24 +1787,44 @@ class ALSCore:
         if u.numel() == 0:
             return {"added": 0, "new_users": empty.to(torch.int32), "new_items":
                     empty.to(torch.int32), "touched_users": empty, "touched_items": empty}
+        return self._add_commit(self._add_compute(u, i, r, seed))
+
+    def _add_compute(self, u, i, r, seed, user_csr=None, item_csr=None, nnz=None) -> dict:
+        """add_ratings steps a-d on device arrays, storing nothing: the grown state of the
+        core's id maps and of the two CSR sides (the core's own blocks, or the (row_ptr, col,
+        val) triples given, which hold `nnz` ratings and may have empty rows: set_ratings
+        passes the sides it has just compacted)."""
+        ub, ib = self.user_block, self.item_block
+        user_csr = user_csr or (ub.row_ptr, ub.col, ub.val)
+        item_csr = item_csr or (ib.row_ptr, ib.col, ib.val)
         uidx, umap, new_u = grow_index(self.uidx, u, self.ws)
         iidx, imap, new_i = grow_index(self.iidx, i, self.ws)
         uk, ik = uidx.keys(u), iidx.keys(i)
-        ub, ib = self.user_block, self.item_block
         add_u = build_csr(uk, uidx, ik, iidx, r, self.ws)
-        user_csr = merge_csr(ub.row_ptr, ub.col, ub.val, ib.n_rows, umap, imap, *add_u)
+        user_csr = merge_csr(*user_csr, ib.n_rows, umap, imap, *add_u)
         add_i = build_csr(ik, iidx, uk, uidx, r, self.ws)
-        item_csr = merge_csr(ib.row_ptr, ib.col, ib.val, ub.n_rows, imap, umap, *add_i)
-        nnz = self.nnz + int(u.numel())
+        item_csr = merge_csr(*item_csr, ub.n_rows, imap, umap, *add_i)
+        nnz = (self.nnz if nnz is None else int(nnz)) + int(u.numel())
         touched_u = (add_u[0][1:] > add_u[0][:-1]).nonzero().flatten()
         touched_i = (add_i[0][1:] > add_i[0][:-1]).nonzero().flatten()
         U = V = None
         if self.rank > 0 and self.U is not None:
             U, V = self._grown_factors(uidx.n, iidx.n, umap, imap, new_u, new_i, user_csr,
                                        item_csr, int(seed))
-        # nothing above touched the core: from here on it cannot fail half-way
-        self.user_block = schedule_block(uidx.n, nnz, *user_csr, self.ws, ub.chunk)
-        self.item_block = schedule_block(iidx.n, nnz, *item_csr, self.ws, ib.chunk)
+        return dict(added=int(u.numel()), uidx=uidx, iidx=iidx, umap=umap, imap=imap,
+                    new_u=new_u, new_i=new_i, user_csr=user_csr, item_csr=item_csr, nnz=nnz,
+                    touched_u=touched_u, touched_i=touched_i, U=U, V=V)
+
+    def _add_commit(self, st: dict) -> dict:
+        """Store what _add_compute made and return add_ratings' report: nothing before this
+        touched the core, and from here on it cannot fail half-way."""
+        uidx, iidx, umap, imap, nnz = st["uidx"], st["iidx"], st["umap"], st["imap"], st["nnz"]
+        new_u, new_i, touched_u, touched_i = (st[k] for k in ("new_u", "new_i", "touched_u",
+                                                              "touched_i"))
+        U, V = st["U"], st["V"]
+        ub, ib = self.user_block, self.item_block
+        self.user_block = schedule_block(uidx.n, nnz, *st["user_csr"], self.ws, ub.chunk)
+        self.item_block = schedule_block(iidx.n, nnz, *st["item_csr"], self.ws, ib.chunk)
         self.uidx, self.iidx, self.nnz = uidx, iidx, nnz
         if U is not None:
             self.U, self.V = U, V
@@ -1742,7 +1839,7 @@ class ALSCore:
         else:
             touched_all = (touched_u, touched_i)
         self._touched = touched_all
-        return {"added": int(u.numel()), "new_users": uidx.ids()[new_u], "new_items":
+        return {"added": st["added"], "new_users": uidx.ids()[new_u], "new_items":
                 iidx.ids()[new_i], "touched_users": touched_u, "touched_items": touched_i}
 
     def _grown_factors(self, n_u, n_i, umap, imap, new_u, new_i, user_csr, item_csr, seed):
@@ -1836,6 +1933,204 @@ class ALSCore:
                                    ("reg", "implicit", "alpha", "nonnegative")))
         kw.update(fit_kwargs)
         return self.fit(self.rank, int(max_iter), U0=self.U[:, :self.rank].clone(), **kw)
+
+    # ---- K18: ratings that are taken back after the fit ----
+    def _listed_pairs(self, users, items, who: str):
+        """The distinct (user, item) pairs of a batch: (u int32, i int32, ur, ir int64 dense
+        rows, -1 = unknown)."""
+        if self.user_block is None:
+            raise ValueError(f"{who} needs the ratings the model was fitted on; this core "
+                             "was built from saved factors (from_factors / load) and has none")
+        u = _to_device(users, torch.int32, self.device)
+        i = _to_device(items, torch.int32, self.device)
+        if u.numel() != i.numel():
+            raise ValueError("users and items must have the same length")
+        if u.numel():
+            key = torch.unique((u.long() << 32) | (i.long() & 0xFFFFFFFF))
+            low = key & 0xFFFFFFFF
+            u = (key >> 32).to(torch.int32)
+            i = torch.where(low >= (1 << 31), low - (1 << 32), low).to(torch.int32)
+        return u, i, self.uidx.rows_of(u), self.iidx.rows_of(i)
+
+    def _mark_removed(self, ur, ir):
+        """Both sides' K18 mark pass for the distinct stored-id pairs (ur, ir) (int64 dense
+        rows).  Returns (user marks, item marks, stored copies dropped per pair in (ur, ir)
+        order of the user side's sort)."""
+        n_u, n_i = self.n_users, self.n_items
+        ub, ib = self.user_block, self.item_block
+        ku = torch.sort(ur * n_i + ir).values            # by user row, then item row
+        ki = torch.sort(ir * n_u + ur).values            # by item row, then user row
+        del_u = _delete_csr(ku // n_i, ku % n_i, n_u)
+        del_i = _delete_csr(ki // n_u, ki % n_u, n_i)
+        mu = remove_mark(ub.row_ptr, ub.col, *del_u, self.ws, count_hits=True)
+        mi = remove_mark(ib.row_ptr, ib.col, *del_i, self.ws)
+        return mu, mi, mu[3]
+
+    def remove_ratings(self, users, items) -> dict:
+        """Take ratings back from the core in place: every stored copy of every listed (user,
+        item) pair goes (a pair listed twice is listed once).  After the call every
+        rating-derived thing — both id maps, both CSR sides and their schedules, nnz — is what
+        ALSCore(the training triples with those pairs filtered out, order kept) would hold,
+        bit for bit:
+          a. ids are mapped to dense rows; a pair with an unknown id is counted as missing
+          b. K18's mark pass (als_csr_remove_mark) flags the stored entries of both sides
+             that stay, against a small delete CSR per side with ascending columns, and
+             gives the kept entries before every row; a listed pair that no stored entry
+             matched is counted as missing as well
+          c. a user or an item left without a rating leaves the model (an empty row would
+             make Spark's lambda * n * I system singular): both id maps shrink
+             (shrink_index: offset and id_space are derived again), the factor rows of the
+             rows that stay move to their new places bit for bit
+          d. K18's compact pass (als_csr_remove_compact) writes each side's kept entries in
+             stored order, columns renumbered through the OTHER side's shrunk map; the row
+             pointer is the kept count before every surviving row, and the side is scheduled
+             again at its current chunk
+          e. everything cached from the ratings (the train exclusion lists, the workspace's
+             rating scale) is dropped.
+        Rows that stay keep their factors until refresh() or refit(); the surviving rows whose
+        rating lists changed join the rows refresh() re-solves, rows touched by earlier adds
+        are renumbered, and those that left are dropped.  Needs one transient second copy of
+        each side's col and val.  An empty batch is a no-op; a call that would remove every
+        rating raises ValueError; nothing is changed when the call raises.
+        Measured on the ML-25M shape (tools/remove_cost.py): 2.5 ms for
+        12 pairs, 3.5 ms for 10^6, 2.9 ms for the busiest user and 3.7 ms for the most-rated
+        item, against 7.9-8.4 ms for ALSCore(the filtered triples): 2.3 to 3.4 times cheaper.
+        Returns {"removed" (stored ratings dropped), "missing" (distinct listed pairs that
+        matched nothing), "left_users", "left_items" (ids, ascending), "touched_users",
+        "touched_items" (int64 dense rows in the new numbering, ascending)}."""
+        u, i, ur, ir = self._listed_pairs(users, items, "remove_ratings")
+        empty = torch.empty(0, dtype=torch.int64, device=self.device)
+        info = {"removed": 0, "missing": int(u.numel()), "left_users": empty.to(torch.int32),
+                "left_items": empty.to(torch.int32), "touched_users": empty,
+                "touched_items": empty}
+        known = (ur >= 0) & (ir >= 0)
+        if not bool(known.any()):
+            return info
+        mu, mi, hits = self._mark_removed(ur[known], ir[known])
+        nnz = int(mu[1][-1])
+        if nnz != int(mi[1][-1]):
+            raise RuntimeError("remove_ratings: the two sides disagree on what stays")
+        if nnz == self.nnz:
+            return info
+        if nnz == 0:
+            raise ValueError("remove_ratings would remove every rating: a model needs one")
+        ub, ib = self.user_block, self.item_block
+        side = []
+        for block, idx, marks in ((ub, self.uidx, mu), (ib, self.iidx, mi)):
+            kept = marks[2][1:] - marks[2][:-1]
+            had = block.row_ptr[1:] - block.row_ptr[:-1]
+            left = (kept == 0).nonzero().flatten()
+            shrunk, mp = shrink_index(idx, left, self.ws)
+            changed = ((kept > 0) & (kept < had)).nonzero().flatten()
+            side.append(dict(idx=shrunk, map=mp, left=idx.ids()[left], kept=kept,
+                             touched=changed if mp is None else mp[changed].long()))
+        su, si = side
+        csr = []
+        for block, marks, me, other, n_cols in ((ub, mu, su, si, ib.n_rows),
+                                                (ib, mi, si, su, ub.n_rows)):
+            col, val = remove_compact(block.col, block.val, marks[0], marks[1], other["map"],
+                                      n_cols, nnz)
+            stays = torch.ones(block.n_rows + 1, dtype=torch.bool, device=self.device)
+            stays[:-1] = me["kept"] > 0               # the last word is nnz
+            csr.append((marks[2][stays].contiguous(), col, val))
+        U = V = None
+        if self.rank > 0 and self.U is not None:
+            U = self.U if su["map"] is None else self.U[su["kept"] > 0].contiguous()
+            V = self.V if si["map"] is None else self.V[si["kept"] > 0].contiguous()
+        # nothing above touched the core: from here on it cannot fail half-way
+        self.user_block = schedule_block(su["idx"].n, nnz, *csr[0], self.ws, ub.chunk)
+        self.item_block = schedule_block(si["idx"].n, nnz, *csr[1], self.ws, ib.chunk)
+        removed, self.nnz = self.nnz - nnz, nnz
+        self.uidx, self.iidx = su["idx"], si["idx"]
+        if U is not None:
+            self.U, self.V = U, V
+        self._train_ex = {}
+        self.ws.rating_scale_key = None   # the largest |rating| may have left
+        touched = []
+        for s, earlier in zip(side, self._touched or (empty, empty)):
+            if s["map"] is not None:      # rows touched earlier, in the new numbering
+                earlier = s["map"][earlier].long()
+                earlier = earlier[earlier >= 0]
+            touched.append(torch.unique(torch.cat([earlier, s["touched"]])))
+        self._touched = tuple(touched)
+        info.update(removed=removed,
+                    missing=int(u.numel()) - int(known.sum()) + int((hits == 0).sum()),
+                    left_users=su["left"], left_items=si["left"], touched_users=su["touched"],
+                    touched_items=si["touched"])
+        return info
+
+    def _remove_rows(self, ids, user_side: bool, who: str) -> dict:
+        if self.user_block is None:
+            raise ValueError(f"{who} needs the ratings the model was fitted on; this core "
+                             "was built from saved factors (from_factors / load) and has none")
+        ids = torch.unique(_to_device(ids, torch.int32, self.device))
+        idx, block, other = ((self.uidx, self.user_block, self.iidx) if user_side else
+                             (self.iidx, self.item_block, self.uidx))
+        rows = idx.rows_of(ids)
+        unknown = int((rows < 0).sum())
+        rows = rows[rows >= 0]
+        row_ptr, col, _ = gather_rows(block.row_ptr, block.col, block.val, rows)
+        mine = torch.repeat_interleave(idx.ids()[rows], row_ptr[1:] - row_ptr[:-1])
+        theirs = other.ids()[col.long()]
+        info = self.remove_ratings(*((mine, theirs) if user_side else (theirs, mine)))
+        info["missing"] += unknown
+        return info
+
+    def remove_users(self, ids) -> dict:
+        """Forget users: remove_ratings of every rating of the listed user ids (their rows
+        expanded into pairs on the device).  An unknown id is counted in "missing"; the
+        users, and every item only they had rated, are in "left_users" / "left_items"."""
+        return self._remove_rows(ids, True, "remove_users")
+
+    def remove_items(self, ids) -> dict:
+        """Withdraw items: remove_users for the other side."""
+        return self._remove_rows(ids, False, "remove_items")
+
+    def set_ratings(self, users, items, ratings, *, seed=0) -> dict:
+        """Replace ratings: every stored copy of each listed pair goes, then the batch is
+        added as add_ratings adds it; of a pair that is several times in the batch the LAST
+        rating wins (the earlier ones are dropped, the order of the rest is kept).  The result
+        is what ALSCore(the old triples without the listed pairs, then the de-duplicated
+        batch) would hold, bit for bit.  A pair that is not stored, or whose ids are new, is
+        simply added.  No row leaves on the way: every row that loses a rating gets one
+        back, so a user whose only rating is replaced keeps the factor row and its bits (K18
+        leaves such a row empty between the two steps, K17 takes empty rows).  The removed
+        state and the added state are computed first and stored at the end: nothing is
+        changed when the call raises.  Returns add_ratings' report for the de-duplicated
+        batch plus "replaced", the stored ratings that went."""
+        if self.user_block is None:
+            raise ValueError("set_ratings needs the ratings the model was fitted on; this core "
+                             "was built from saved factors (from_factors / load) and has none")
+        u = _to_device(users, torch.int32, self.device)
+        i = _to_device(items, torch.int32, self.device)
+        r = _to_device(ratings, torch.float32, self.device)
+        if not (u.numel() == i.numel() == r.numel()):
+            raise ValueError("users, items and ratings must have the same length")
+        if u.numel() == 0:
+            return dict(self.add_ratings(u, i, r), replaced=0)
+        key = (u.long() << 32) | (i.long() & 0xFFFFFFFF)
+        uniq, inv = torch.unique(key, return_inverse=True)
+        last = torch.full((uniq.numel(),), -1, dtype=torch.int64, device=self.device)
+        last.scatter_reduce_(0, inv, torch.arange(key.numel(), device=self.device), "amax")
+        pick = torch.sort(last).values                   # last occurrences, in batch order
+        u, i, r = u[pick].contiguous(), i[pick].contiguous(), r[pick].contiguous()
+        ur, ir = self.uidx.rows_of(u), self.iidx.rows_of(i)
+        known = (ur >= 0) & (ir >= 0)
+        ucsr = icsr = None
+        nnz = self.nnz
+        if bool(known.any()):
+            mu, mi, _ = self._mark_removed(ur[known], ir[known])
+            nnz = int(mu[1][-1])
+            if nnz != int(mi[1][-1]):
+                raise RuntimeError("set_ratings: the two sides disagree on what stays")
+            if nnz != self.nnz:   # rows stay where they are, empty or not: no map, no shrink
+                ub, ib = self.user_block, self.item_block
+                ucsr = (mu[2],) + remove_compact(ub.col, ub.val, mu[0], mu[1], None, ib.n_rows, nnz)
+                icsr = (mi[2],) + remove_compact(ib.col, ib.val, mi[0], mi[1], None, ub.n_rows, nnz)
+        replaced = self.nnz - nnz
+        info = self._add_commit(self._add_compute(u, i, r, seed, ucsr, icsr, nnz))
+        info["replaced"] = replaced
+        return info
 
     def fingerprint(self) -> dict:
         """Order-independent identity of the training ratings (checkpoint matching)."""

@@ -186,6 +186,15 @@ def reject_sharded_update() -> None:
         "yet: ratings are added in place on the single-GPU engine, an ALSCore")
 
 
+def reject_sharded_remove() -> None:
+    """The sharded engine carries remove_ratings / remove_users / remove_items / set_ratings
+    with the single-GPU signature and refuses them, as it refuses add_ratings."""
+    raise NotImplementedError(
+        "remove_ratings / remove_users / remove_items / set_ratings are not supported by the "
+        "sharded engine (ShardedALS) yet: ratings are removed and replaced in place on the "
+        "single-GPU engine, an ALSCore")
+
+
 def reject_sharded_rating_stats() -> None:
     """The sharded engine carries rating_stats / global_stats / top_rated / fit_baseline with
     the single-GPU signature and refuses them, as it refuses list_metrics."""

@@ -307,7 +307,8 @@ class ALSModel:
         return self._core.objective(float(p["regParam"]), bool(p["implicitPrefs"]),
                                     float(p["alpha"]))
 
-    def update(self, dataset, maxIter: int = 2, mode: str = "refit") -> "ALSModel":
+    def update(self, dataset, maxIter: int = 2, mode: str = "refit", replace: bool = False
+               ) -> "ALSModel":
         """Add the ratings of `dataset` (this model's userCol / itemCol / ratingCol) to the
         model's training data and bring the factors up to date, without building the model
         again (K17, ALSCore.add_ratings).  THIS MODEL IS CHANGED IN PLACE and returned; new
@@ -320,14 +321,21 @@ class ALSModel:
                         else keeps their factors (ALSCore.refresh)
               "none"    the ratings are merged and new rows get fold-in factors; nothing
                         else moves.
+        replace=True: a rating of a (user, item) pair the model already holds takes the
+        place of every stored one instead of standing beside it, and of a pair that is
+        several times in `dataset` the last counts (K18, ALSCore.set_ratings).
         Not on a loaded model (no training data) nor on the sharded engine."""
         if mode not in ("refit", "refresh", "none"):
             raise ValueError(f"mode must be 'refit', 'refresh' or 'none', got {mode!r}")
         p = self._p
         u, i, r = columns_of(dataset, (p["userCol"], p["itemCol"], p["ratingCol"]))
         seed = _DEFAULT_SEED if p["seed"] is None else int(p["seed"])
-        self._core.add_ratings(check_integers(u, p["userCol"]), check_integers(i, p["itemCol"]),
-                               to_float32(r), seed=seed)
+        change = self._core.set_ratings if replace else self._core.add_ratings
+        change(check_integers(u, p["userCol"]), check_integers(i, p["itemCol"]), to_float32(r),
+               seed=seed)
+        return self._bring_up_to_date(maxIter, mode)
+
+    def _bring_up_to_date(self, maxIter, mode) -> "ALSModel":
         if mode == "refit":
             observe = {"objective_every": self._objective_every} if self._objective_every else {}
             self._core.refit(int(maxIter), **observe)
@@ -335,6 +343,37 @@ class ALSModel:
         elif mode == "refresh":
             self._core.refresh()
         return self
+
+    def remove(self, dataset, maxIter: int = 2, mode: str = "refit") -> "ALSModel":
+        """Take the ratings of the (userCol, itemCol) pairs of `dataset` out of the model's
+        training data — every stored rating of each pair — and bring the factors up to date
+        without building the model again (K18, ALSCore.remove_ratings).  THIS MODEL IS
+        CHANGED IN PLACE and returned.  A user or item left without a rating leaves
+        userFactors / itemFactors; a pair the model does not hold is ignored.  mode as in
+        update(): "refit", "refresh" (only the users and items that lost a rating are solved
+        again) or "none".  Not on a loaded model nor on the sharded engine."""
+        if mode not in ("refit", "refresh", "none"):
+            raise ValueError(f"mode must be 'refit', 'refresh' or 'none', got {mode!r}")
+        p = self._p
+        u, i = columns_of(dataset, (p["userCol"], p["itemCol"]))
+        self._core.remove_ratings(check_integers(u, p["userCol"]),
+                                  check_integers(i, p["itemCol"]))
+        return self._bring_up_to_date(maxIter, mode)
+
+    def removeUsers(self, ids, maxIter: int = 2, mode: str = "refit") -> "ALSModel":
+        """remove() of every rating of the listed user ids: they leave the model, and so
+        does an item only they had rated."""
+        if mode not in ("refit", "refresh", "none"):
+            raise ValueError(f"mode must be 'refit', 'refresh' or 'none', got {mode!r}")
+        self._core.remove_users(check_integers(np.asarray(list(ids)), self._p["userCol"]))
+        return self._bring_up_to_date(maxIter, mode)
+
+    def removeItems(self, ids, maxIter: int = 2, mode: str = "refit") -> "ALSModel":
+        """remove() of every rating of the listed item ids."""
+        if mode not in ("refit", "refresh", "none"):
+            raise ValueError(f"mode must be 'refit', 'refresh' or 'none', got {mode!r}")
+        self._core.remove_items(check_integers(np.asarray(list(ids)), self._p["itemCol"]))
+        return self._bring_up_to_date(maxIter, mode)
 
     def _factors_df(self, ids, F):
         import pandas as pd

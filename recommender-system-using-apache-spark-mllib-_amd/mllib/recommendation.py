@@ -51,6 +51,13 @@ def _triples(ratings):
     return check_integers(u, "user"), check_integers(i, "product"), to_float32(r)
 
 
+def _check_mode(mode, iterations) -> None:
+    if mode not in ("refit", "refresh", "none"):
+        raise ValueError(f"mode must be 'refit', 'refresh' or 'none', got {mode!r}")
+    if int(iterations) < 0:
+        raise ValueError(f"iterations must be >= 0, got {iterations}")
+
+
 def _pairs(user_product):
     if hasattr(user_product, "to_numpy"):
         user_product = user_product.to_numpy()
@@ -337,7 +344,7 @@ class MatrixFactorizationModel:
                   for a, b, c in zip(ids[r, :n[r]], rat[r, :n[r]], con[r, :n[r]])])
                 for r in range(len(uu))]
 
-    def update(self, ratings, iterations: int = 2, mode: str = "refit"
+    def update(self, ratings, iterations: int = 2, mode: str = "refit", replace: bool = False
                ) -> "MatrixFactorizationModel":
         """Add `ratings` (tuples or Ratings, as ALS.train takes them) to the model's training
         data and bring the factors up to date without training again — the reference's
@@ -346,18 +353,52 @@ class MatrixFactorizationModel:
         mode: "refit" = `iterations` warm iterations over all rows from the current user
         features, with the lambda / implicit / alpha / solver it was trained with;
         "refresh" = only the users and products of `ratings` are solved again; "none" = the
-        ratings are merged and new ids get fold-in features.  Not on a loaded model."""
-        if mode not in ("refit", "refresh", "none"):
-            raise ValueError(f"mode must be 'refit', 'refresh' or 'none', got {mode!r}")
-        if int(iterations) < 0:
-            raise ValueError(f"iterations must be >= 0, got {iterations}")
+        ratings are merged and new ids get fold-in features.  replace=True: a rating of a
+        (user, product) pair the model already holds takes the place of every stored one
+        instead of standing beside it, and of a pair that is several times in `ratings` the
+        last counts (K18, ALSCore.set_ratings).  Not on a loaded model."""
+        _check_mode(mode, iterations)
         u, i, r = _triples(ratings)
-        self._core.add_ratings(u, i, r, seed=_DEFAULT_SEED)
+        if replace:
+            self._core.set_ratings(u, i, r, seed=_DEFAULT_SEED)
+        else:
+            self._core.add_ratings(u, i, r, seed=_DEFAULT_SEED)
+        return self._bring_up_to_date(mode, iterations)
+
+    def _bring_up_to_date(self, mode, iterations) -> "MatrixFactorizationModel":
         if mode == "refit":
             self._core.refit(int(iterations))
         elif mode == "refresh":
             self._core.refresh()
         return self
+
+    def remove(self, user_product, iterations: int = 2, mode: str = "refit"
+               ) -> "MatrixFactorizationModel":
+        """Take the ratings of the listed (user, product) pairs out of the model's training
+        data — every stored rating of each pair — and bring the features up to date without
+        training again (K18, ALSCore.remove_ratings).  THIS MODEL IS CHANGED IN PLACE and
+        returned.  A user or product left without a rating leaves the model; a pair the
+        model does not hold is ignored.  mode as in update(): "refit", "refresh" (only the
+        users and products that lost a rating are solved again) or "none".  Not on a loaded
+        model."""
+        _check_mode(mode, iterations)
+        self._core.remove_ratings(*_pairs(user_product))
+        return self._bring_up_to_date(mode, iterations)
+
+    def removeUsers(self, users, iterations: int = 2, mode: str = "refit"
+                    ) -> "MatrixFactorizationModel":
+        """remove() of every rating of the listed users: they leave the model, and so does a
+        product only they had rated."""
+        _check_mode(mode, iterations)
+        self._core.remove_users(check_integers(np.asarray(list(users)), "user"))
+        return self._bring_up_to_date(mode, iterations)
+
+    def removeProducts(self, products, iterations: int = 2, mode: str = "refit"
+                       ) -> "MatrixFactorizationModel":
+        """remove() of every rating of the listed products."""
+        _check_mode(mode, iterations)
+        self._core.remove_items(check_integers(np.asarray(list(products)), "product"))
+        return self._bring_up_to_date(mode, iterations)
 
     def save(self, sc, path: str, overwrite: bool = False) -> None:
         """MatrixFactorizationModel.save(sc, path) in Spark's layout (``sc`` is ignored)."""

@@ -194,15 +194,18 @@ def similar_movies(model, movie_ids: Iterable[int], movies: Iterable[Sequence], 
 
 def personal_recommendations_update(model, user_id: int, rated: Iterable[Sequence],
                                     movies: Iterable[Sequence], num: int = 20,
-                                    min_ratings: int = 75, iterations: int = 2
-                                    ) -> List[Tuple[float, str, int]]:
+                                    min_ratings: int = 75, iterations: int = 2,
+                                    replace: bool = False) -> List[Tuple[float, str, int]]:
     """R:207-247 without building the model again: the user's ratings are added to the
     model's own training data (K17, ALSCore.add_ratings), the model is refitted warm for
     `iterations` iterations from its current user factors (ALSCore.refit), and the list is
     personal_recommendations' — (predicted rating, movie name, number of ratings) of the
     user's top `num` unrated movies with more than `min_ratings` ratings.  The counts are
     the engine's own statistics (K16) after the merge, so the ratings just added count.
-    THE MODEL IS CHANGED IN PLACE: it now knows the user.
+    THE MODEL IS CHANGED IN PLACE: it now knows the user.  replace=True: a rating of a movie
+    the user had rated before takes the place of the stored one (K18, ALSCore.set_ratings)
+    instead of standing beside it — the call to make when the user comes back and changes
+    their mind.
 
     rated:  the user's (user, movie, rating) triples (myRatedMovies, R:190-202), all of
             `user_id`
@@ -213,7 +216,8 @@ def personal_recommendations_update(model, user_id: int, rated: Iterable[Sequenc
     eng = _engine_of(model)
     if rated:
         u, m, r = (np.asarray(x) for x in zip(*rated))
-        eng.add_ratings(u.astype(np.int32), m.astype(np.int32), r.astype(np.float32))
+        change = eng.set_ratings if replace else eng.add_ratings
+        change(u.astype(np.int32), m.astype(np.int32), r.astype(np.float32))
         eng.refit(int(iterations))
     stats = eng.rating_stats(user_side=False)
     counts = dict(zip(stats["ids"].cpu().numpy().tolist(),
