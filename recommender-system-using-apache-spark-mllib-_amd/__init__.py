@@ -13,7 +13,8 @@ Surfaces (mirroring pyspark's module layout):
   als_mi355x.ml.evaluation         RankingEvaluator, RegressionEvaluator
   als_mi355x.ml.tuning             ParamGridBuilder, TrainValidationSplit, CrossValidator
   als_mi355x.mllib.evaluation      RankingMetrics, RegressionMetrics
-  als_mi355x.engine                ALSCore — the device-resident engine
+  als_mi355x.engine                ALSCore — the device-resident engine (re-exports the bindings)
+  als_mi355x.kernels.*             one ctypes binding module per kernel family of libals_hip.so
   als_mi355x.distributed           one-process-per-GPU sharded ALS (RCCL all-gather)
 """
 __version__ = "0.1.0"

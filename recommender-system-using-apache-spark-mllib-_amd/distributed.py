@@ -43,7 +43,7 @@ from typing import Optional
 import torch
 import torch.distributed as dist
 
-from .engine import id_offset
+from .kernels.csr import id_offset
 from .filters import (reject_sharded_diversify, reject_sharded_explain, reject_sharded_filters,
                       reject_sharded_fold_in,
                       reject_sharded_full_rank, reject_sharded_list_metrics,

@@ -16,9 +16,7 @@ Data layout in HBM (DESIGN.md "Data layout"):
 """
 from __future__ import annotations
 
-import ctypes
 import math
-from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
@@ -26,1400 +24,46 @@ import torch
 
 from . import _lib
 from . import filters as _filters
-from ._lib import check, ptr, stream_ptr
+from ._lib import check, ptr, stream_ptr  # noqa: F401 (re-exported, as the bindings below)
+# every binding stays reachable as engine.NAME: bench.py, the tests and tools/ go through here
+from .kernels.workspace import ld_for, Workspace, _to_device, k_pad, raise_status, _host_f64
+from .kernels.csr import (
+    IdIndex, MAX_ID_SPACE, id_offset, build_index, build_csr, csr_merge_tile, merge_csr,
+    grow_index, csr_remove_tile, remove_mark, remove_compact, shrink_index, _delete_csr,
+    gather_rows, group_pairs,
+)
+from .kernels.schedule import (
+    DEFAULT_CHUNK, chunk_for, DUAL_MAX_RATINGS, DUAL_MAX_RATINGS_64, dual_limit, RatingBlock,
+    build_block, schedule_block,
+)
+from .kernels.solve import (
+    MAX_RANK, PHASE_LAUNCH1, PHASE_LAUNCH2, PHASE_PREP, PHASE_RSCALE, PHASE_DUAL, PHASE_RESCUE,
+    PHASE_ALL, compute_yty, solve_half, SplitSchedule, _segment_tasks, split_schedule,
+    solve_half_split,
+)
+from .kernels.rows import fold_in_rows, nnls_rows, EXPLAIN_MAX_TOP, explain_rows
+from .kernels.predict import (
+    predict_pairs, rmse_pairs, MOMENT_NAMES, regression_moments_pairs, regression_moments_cols,
+    regression_dict,
+)
+from .kernels.topk import (
+    ids_of, topk_rows, topk_rows_filtered, SIMILAR_MAX_TOP, SIMILAR_MAX_SLICES,
+    SIMILAR_SWEEP_MIN_ROWS, similar_rows, unit_rows, similar_rows_unit, DIVERSIFY_MAX_POOL,
+    DIVERSIFY_POOL_BYTES, _check_lists, diversify_rows, list_similarity_rows,
+)
+from .kernels.ranking import (
+    LIST_MAX_AT, LIST_METRIC_FIELDS, _list_rows_args, list_exposure_window, list_exposure_rows,
+    list_concentration, list_novelty_rows, long_tail_bits, list_metrics_dict, list_metrics_rows,
+    MAX_RANK_AT, rank_metrics_rows, rank_metrics_dict, FULL_RANK_SUMS, rank_positions_table,
+    rank_positions_rows, full_rank_sums_rows, full_rank_dict,
+)
+from .kernels.objective import OBJECTIVE_SIDE, objective_span, objective_side, gram_dot
+from .kernels.stats import (
+    RATING_MOMENTS, BASELINE_METHODS, rating_stats_task, rating_stats_group_rows, row_moments,
+    bias_update, baseline_predict_rows, rating_stats_dict, Baseline,
+)
 
-DEFAULT_CHUNK = 4096  # ratings per heavy-row task (round 5: profiles/r05/ab_chunk*.jsonl)
 
-
-def chunk_for(rank: int, implicit: bool) -> int:
-    """Heavy-row task length of a half-sweep (ALSCore's default): a task's fp32 partial
-    slot grows as k^2, so explicit fits at rank > 64 take four times the ratings per slot.
-    Measured round 5 (profiles/r05/ab_chunk2.jsonl, ab_chunk3.jsonl): configs[3] (k = 128,
-    explicit) 4096 / 8192 / 16384 ratings 275.1 / 270.6 / 266.3 ms/iter; at configs[1]
-    (k = 64) 8192 took the longest rows' error to 1.2e-6 and at configs[2] (implicit) the
-    >2048-rating rows sit at 8e-7 with 4096 already, so those keep 4096."""
-    return 4 * DEFAULT_CHUNK if (rank > 64 and not implicit) else DEFAULT_CHUNK
-MAX_RANK = 128       # k <= 64: gram_solve_kernel; 64 < k <= 128: W1 (one wavefront per system)
-DUAL_MAX_RATINGS = 96  # explicit, 64 < k <= 128: rows this short go through the n x n dual
-# (round 5, configs[3]: limit 64 / 80 / 96 -> 288.9 / 275.8 / 267.2 ms/iter, profiles/r05/ab_dual_limit.jsonl)
-DUAL_MAX_RATINGS_64 = 32  # explicit, 32 < k <= 64: the same for rows this short
-
-# als_solve_half phase bits (include/als_hip.h ALS_PHASE_*)
-PHASE_LAUNCH1, PHASE_LAUNCH2, PHASE_PREP, PHASE_RSCALE, PHASE_DUAL, PHASE_RESCUE = 1, 2, 4, 8, 16, 32
-PHASE_ALL = 63
-
-
-def dual_limit(rank: int) -> int:
-    """Longest row (ratings) solved through the n x n dual system at this rank; 0 = none.
-    The dual system Y_S Y_S^T + lambda n I is full rank only while n <= rank: a longer
-    row would trade the full-rank k x k primal for a rank-deficient n x n system whose
-    smallest eigenvalues are lambda n (fp32 error growing as lambda shrinks), so the
-    limit is min(96, rank) above rank 64 and 32 (< rank) at ranks 33-64."""
-    if rank > 64:
-        return min(DUAL_MAX_RATINGS, rank)
-    return DUAL_MAX_RATINGS_64 if rank > 32 else 0
-
-
-def ld_for(rank: int) -> int:
-    return (rank + 3) // 4 * 4
-
-
-class Workspace:
-    """One growable device scratch buffer; the library never allocates on a compute call.
-
-    shared_rating_scale: every block solved with this workspace has the same ratings
-    (ALSCore's user- and item-major CSR of one rating set), so the rating scale word
-    that als_solve_half's phase 8 leaves at the start of the buffer stays valid until
-    another call uses the buffer or it is reallocated; solve_half then skips phase 8."""
-
-    def __init__(self, device, shared_rating_scale: bool = False):
-        self.device = device
-        self.buf: Optional[torch.Tensor] = None
-        self.shared_rating_scale = shared_rating_scale
-        self.rating_scale_key = None
-
-    def get(self, nbytes: int, keep_scale: bool = False) -> torch.Tensor:
-        nbytes = max(int(nbytes), 256)
-        if self.buf is None or self.buf.numel() < nbytes:
-            self.buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            # the scale / rescue-count words: a call without PREP on a fresh buffer
-            # must not start from garbage
-            self.buf[:256].zero_()
-            self.rating_scale_key = None
-        if not keep_scale:
-            self.rating_scale_key = None
-        return self.buf
-
-
-def _to_device(x, dtype, device) -> torch.Tensor:
-    if isinstance(x, torch.Tensor):
-        return x.to(device=device, dtype=dtype).contiguous()
-    return torch.as_tensor(np.ascontiguousarray(np.asarray(x)), device=device).to(dtype).contiguous()
-
-
-# ---------------------------------------------------------------------------
-# K1: id maps, CSR, schedule
-# ---------------------------------------------------------------------------
-@dataclass
-class IdIndex:
-    """Dense id map of one side (the device form of Spark's sorted InBlock.srcIds).
-
-    Spark accepts any Int id (negative ones included).  The map is indexed by
-    `id - offset`; `offset` is the smallest id when ids are negative or the id
-    range starts far above 0, else 0 (ids used directly)."""
-    map: torch.Tensor       # int32 [id_space], (id - offset) -> dense row or -1
-    uniq: torch.Tensor      # int32 [n]   ascending ids - offset
-    n: int
-    offset: int = 0
-
-    @property
-    def id_space(self) -> int:
-        return int(self.map.numel())
-
-    def ids(self) -> torch.Tensor:
-        """The original ids of the dense rows (ascending), int32."""
-        return self.uniq if self.offset == 0 else (self.uniq.long() + self.offset).to(torch.int32)
-
-    def rows_of(self, ids: torch.Tensor) -> torch.Tensor:
-        """Dense row (int64) of each id, -1 when unknown."""
-        k = ids.long() - self.offset
-        ok = (k >= 0) & (k < self.id_space)
-        out = torch.full_like(k, -1)
-        out[ok] = self.map[k[ok]].long()
-        return out
-
-    def keys(self, ids: torch.Tensor) -> torch.Tensor:
-        """Query ids -> map keys; ids outside the mapped range -> -1 (unknown)."""
-        if self.offset == 0:
-            return ids.to(torch.int32).contiguous()
-        s = ids.long() - self.offset
-        return torch.where((s >= 0) & (s < self.id_space), s, -1).to(torch.int32).contiguous()
-
-
-MAX_ID_SPACE = 2 ** 31 - 1   # the map is indexed by int32
-
-
-def id_offset(lo: int, hi: int) -> int:
-    """Map offset for ids in [lo, hi]: 0 for the usual non-negative, compact ids."""
-    off = 0 if (lo >= 0 and hi < (1 << 26)) else lo
-    if hi - off + 1 > MAX_ID_SPACE:
-        raise ValueError(f"id range [{lo}, {hi}] spans more than 2^31-1 values; this build "
-                         "indexes ids through a dense int32 map")
-    return off
-
-
-def build_index(ids: torch.Tensor, id_space: int, ws: Workspace) -> IdIndex:
-    L = _lib.lib()
-    dev = ids.device
-    mp = torch.empty(id_space, dtype=torch.int32, device=dev)
-    uniq = torch.empty(id_space, dtype=torch.int32, device=dev)
-    nu = torch.zeros(1, dtype=torch.int32, device=dev)
-    need = L.als_index_workspace_bytes(ids.numel(), id_space)
-    w = ws.get(need)
-    check(L.als_index_build(ptr(ids), ids.numel(), id_space, ptr(mp), ptr(uniq), ptr(nu), ptr(w),
-                            w.numel(), stream_ptr(dev)), "als_index_build")
-    n = int(nu.item())
-    return IdIndex(mp, uniq[:n].clone(), n)
-
-
-@dataclass
-class RatingBlock:
-    """One side's ratings in HBM as CSR plus its half-sweep work schedule."""
-    n_rows: int
-    nnz: int
-    row_ptr: torch.Tensor
-    col: torch.Tensor
-    val: torch.Tensor
-    chunk: int
-    n_light: int
-    n_heavy: int
-    n_chunks: int
-    light_rows: torch.Tensor
-    heavy_rows: torch.Tensor
-    heavy_slot_begin: torch.Tensor
-    chunk_row: torch.Tensor
-    chunk_begin: torch.Tensor
-    chunk_end: torch.Tensor
-    # short_counts[d] = light rows with <= d ratings, d = 0..DUAL_MAX_RATINGS (host ints)
-    short_counts: tuple = ()
-    short_nnz: tuple = ()   # ratings of those rows
-
-    @property
-    def n_short(self) -> int:
-        return self.short_counts[-1] if self.short_counts else 0
-
-    def n_dual(self, rank: int) -> int:
-        """Light rows solved through the n x n dual system at this rank (explicit, reg > 0):
-        the tail of the longest-first light list with <= dual_limit(rank) ratings."""
-        d = dual_limit(rank)
-        return self.short_counts[d] if (d and self.short_counts) else 0
-
-    def dual_nnz(self, rank: int) -> int:
-        """Ratings of the dual-path rows at this rank."""
-        d = dual_limit(rank)
-        return self.short_nnz[d] if (d and self.short_nnz) else 0
-
-
-def build_csr(row_ids: torch.Tensor, row_index: IdIndex, col_ids: torch.Tensor,
-              col_index: IdIndex, vals: torch.Tensor, ws: Workspace):
-    """K1 (als_csr_build) alone: (row_ptr int64 [n + 1], col int32, val f32) of one side,
-    without a schedule."""
-    L = _lib.lib()
-    dev = row_ids.device
-    nnz = int(row_ids.numel())
-    n_rows = row_index.n
-    row_ptr = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
-    col = torch.empty(nnz, dtype=torch.int32, device=dev)
-    val = torch.empty(nnz, dtype=torch.float32, device=dev)
-    w = ws.get(L.als_csr_workspace_bytes(nnz, n_rows))
-    check(L.als_csr_build(ptr(row_ids), ptr(row_index.map), ptr(col_ids), ptr(col_index.map),
-                          ptr(vals), nnz, n_rows, ptr(row_ptr), ptr(col), ptr(val), ptr(w),
-                          w.numel(), stream_ptr(dev)), "als_csr_build")
-    return row_ptr, col, val
-
-
-def build_block(row_ids: torch.Tensor, row_index: IdIndex, col_ids: torch.Tensor,
-                col_index: IdIndex, vals: torch.Tensor, ws: Workspace,
-                chunk: int = DEFAULT_CHUNK) -> RatingBlock:
-    row_ptr, col, val = build_csr(row_ids, row_index, col_ids, col_index, vals, ws)
-    return schedule_block(row_index.n, int(row_ids.numel()), row_ptr, col, val, ws, chunk)
-
-
-def csr_merge_tile() -> int:
-    """Output entries per workgroup of als_csr_merge (tests size their shapes from it)."""
-    return int(_lib.lib().als_csr_merge_tile())
-
-
-def merge_csr(row_ptr_old, col_old, val_old, n_cols_old: int, row_map, col_map, row_ptr_add,
-              col_add, val_add):
-    """K17 (als_csr_merge): the CSR K1 would build from concat(old ratings, batch), from the
-    old side's CSR and the batch's CSR (built by K1 against the grown id maps), in one pass
-    with no sort.  row_map / col_map: int32 [n_old] / [n_cols_old], the dense row each old
-    row of this / the other side has after the growth, None where the side gained no id.
-    Returns (row_ptr int64 [n_new + 1], col int32, val f32); the contract is in
-    include/als_hip.h."""
-    L = _lib.lib()
-    dev = row_ptr_old.device
-    n_old, n_new = int(row_ptr_old.numel()) - 1, int(row_ptr_add.numel()) - 1
-    nnz_old, nnz_add = int(col_old.numel()), int(col_add.numel())
-    row_ptr = torch.empty(n_new + 1, dtype=torch.int64, device=dev)
-    col = torch.empty(nnz_old + nnz_add, dtype=torch.int32, device=dev)
-    val = torch.empty(nnz_old + nnz_add, dtype=torch.float32, device=dev)
-    check(L.als_csr_merge(ptr(row_ptr_old), ptr(col_old), ptr(val_old), nnz_old, n_old,
-                          int(n_cols_old), ptr(row_map), ptr(col_map), ptr(row_ptr_add),
-                          ptr(col_add), ptr(val_add), nnz_add, n_new, ptr(row_ptr), ptr(col),
-                          ptr(val), stream_ptr(dev)), "als_csr_merge")
-    return row_ptr, col, val
-
-
-def grow_index(index: IdIndex, ids: torch.Tensor, ws: Workspace):
-    """The id map of `index`'s ids plus `ids` (int32 original ids, device), as a fresh
-    build_index over the union would make it: (grown IdIndex, new_of_old, new_rows).
-    new_of_old: int32 [index.n], the dense row each old row has now (strictly increasing),
-    None when no id is new; new_rows: int64, the dense rows of the new ids, ascending.  A new
-    id below the old offset, or a negative one, re-bases the map (id_offset of the union)."""
-    dev = ids.device
-    old_lo, old_hi = int(index.uniq[0]) + index.offset, int(index.uniq[-1]) + index.offset
-    lo, hi = min(old_lo, int(ids.min())), max(old_hi, int(ids.max()))
-    off = id_offset(lo, hi)
-    old_keys = (index.uniq.long() + (index.offset - off))
-    keys = torch.cat([old_keys, ids.long() - off]).to(torch.int32).contiguous()
-    grown = build_index(keys, hi - off + 1, ws)
-    grown.offset = off
-    if grown.n == index.n:
-        return grown, None, torch.empty(0, dtype=torch.int64, device=dev)
-    new_of_old = grown.map[old_keys].contiguous()
-    is_new = torch.ones(grown.n, dtype=torch.bool, device=dev)
-    is_new[new_of_old.long()] = False
-    return grown, new_of_old, is_new.nonzero().flatten()
-
-
-def csr_remove_tile() -> int:
-    """Stored entries per workgroup of K18 (tests size their shapes from it)."""
-    return int(_lib.lib().als_csr_remove_tile())
-
-
-def remove_mark(row_ptr_old, col_old, row_ptr_del, col_del, ws: Workspace, count_hits=False):
-    """K18, first call (als_csr_remove_mark): which stored entries of one side stay when the
-    pairs of the delete CSR (row_ptr_del int64 [n + 1], col_del int32, every row's columns
-    ascending; both None = delete nothing) leave.  Returns (keep_bits, tile_off, row_ptr_kept,
-    del_hits): one bit per stored entry (int64 words holding the uint64 bits), the exclusive
-    scan of the tiles' kept counts (tile_off[-1] = the entries that stay), the kept entries
-    before every old row, and with count_hits the stored copies dropped per listed pair
-    (else None).  The contract is in include/als_hip.h."""
-    L = _lib.lib()
-    dev = row_ptr_old.device
-    n_old, nnz_old = int(row_ptr_old.numel()) - 1, int(col_old.numel())
-    nnz_del = 0 if col_del is None else int(col_del.numel())
-    tiles = -(-nnz_old // csr_remove_tile())
-    keep_bits = torch.empty(-(-nnz_old // 64), dtype=torch.int64, device=dev)
-    tile_off = torch.empty(tiles + 1, dtype=torch.int64, device=dev)
-    row_ptr_kept = torch.empty(n_old + 1, dtype=torch.int64, device=dev)
-    hits = torch.empty(nnz_del, dtype=torch.int32, device=dev) if count_hits else None
-    w = ws.get(L.als_csr_remove_scratch_bytes(nnz_old, n_old))
-    check(L.als_csr_remove_mark(ptr(row_ptr_old), ptr(col_old), nnz_old, n_old, ptr(row_ptr_del),
-                                ptr(col_del), nnz_del, ptr(keep_bits), ptr(tile_off),
-                                ptr(row_ptr_kept), ptr(hits), ptr(w), w.numel(), stream_ptr(dev)),
-          "als_csr_remove_mark")
-    return keep_bits, tile_off, row_ptr_kept, hits
-
-
-def remove_compact(col_old, val_old, keep_bits, tile_off, col_map, n_cols_old: int,
-                   nnz_out: int):
-    """K18, second call (als_csr_remove_compact): (col int32 [nnz_out], val f32 [nnz_out]), the
-    kept entries in their stored order, columns passed through col_map (int32 [n_cols_old], the
-    dense row each old row of the other side has now, None = unchanged)."""
-    L = _lib.lib()
-    dev = col_old.device
-    col = torch.empty(int(nnz_out), dtype=torch.int32, device=dev)
-    val = torch.empty(int(nnz_out), dtype=torch.float32, device=dev)
-    check(L.als_csr_remove_compact(ptr(col_old), ptr(val_old), int(col_old.numel()),
-                                   ptr(keep_bits), ptr(tile_off), ptr(col_map), int(n_cols_old),
-                                   ptr(col), ptr(val), int(nnz_out), stream_ptr(dev)),
-          "als_csr_remove_compact")
-    return col, val
-
-
-def shrink_index(index: IdIndex, leaving_rows: torch.Tensor, ws: Workspace):
-    """The mirror of grow_index: the id map of `index` without the dense rows `leaving_rows`
-    (int64, device), as a fresh build_index over the remaining ids would make it — offset and
-    id_space are derived again, so they move when the smallest or the largest id leaves.
-    Returns (IdIndex, new_of_old): new_of_old int32 [index.n], the dense row each old row has
-    now, -1 for a row that left; (index, None) when none leaves.  At least one row must stay."""
-    if leaving_rows.numel() == 0:
-        return index, None
-    dev = index.uniq.device
-    stay = torch.ones(index.n, dtype=torch.bool, device=dev)
-    stay[leaving_rows] = False
-    ids = index.uniq[stay].long() + index.offset
-    if ids.numel() == 0:
-        raise ValueError("shrink_index: every row leaves")
-    lo, hi = int(ids[0]), int(ids[-1])
-    off = id_offset(lo, hi)
-    shrunk = build_index((ids - off).to(torch.int32).contiguous(), hi - off + 1, ws)
-    shrunk.offset = off
-    new_of_old = torch.full((index.n,), -1, dtype=torch.int32, device=dev)
-    new_of_old[stay] = torch.arange(shrunk.n, dtype=torch.int32, device=dev)
-    return shrunk, new_of_old
-
-
-def _delete_csr(rows: torch.Tensor, cols: torch.Tensor, n_rows: int):
-    """(row_ptr int64 [n_rows + 1], col int32) of distinct (row, col) pairs that are sorted by
-    row, then column: every row's columns ascending, as als_csr_remove_mark wants them."""
-    row_ptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=rows.device)
-    row_ptr[1:] = torch.cumsum(torch.bincount(rows, minlength=n_rows), 0)
-    return row_ptr, cols.to(torch.int32).contiguous()
-
-
-def gather_rows(row_ptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, rows: torch.Tensor):
-    """The ragged rows `rows` (int64 dense rows) of a CSR as a CSR of their own, each row's
-    entries in its stored order: (row_ptr int64 [m + 1], col int32, val f32), the input of
-    fold_in_rows / nnls_rows."""
-    beg = row_ptr[rows]
-    ln = row_ptr[rows + 1] - beg
-    out_ptr = torch.zeros(rows.numel() + 1, dtype=torch.int64, device=row_ptr.device)
-    out_ptr[1:] = torch.cumsum(ln, 0)
-    src = torch.repeat_interleave(beg - out_ptr[:-1], ln) + torch.arange(
-        int(out_ptr[-1]), device=row_ptr.device)
-    return out_ptr, col[src].contiguous(), val[src].contiguous()
-
-
-def schedule_block(n_rows, nnz, row_ptr, col, val, ws: Workspace, chunk: int = DEFAULT_CHUNK
-                   ) -> RatingBlock:
-    L = _lib.lib()
-    dev = row_ptr.device
-    counts = torch.zeros(3, dtype=torch.int32, device=dev)
-    check(L.als_schedule_count(ptr(row_ptr), n_rows, chunk, ptr(counts), stream_ptr(dev)),
-          "als_schedule_count")
-    n_light, n_heavy, n_chunks = (int(x) for x in counts.tolist())
-    i32 = dict(dtype=torch.int32, device=dev)
-    light = torch.empty(max(n_light, 1), **i32)
-    heavy = torch.empty(max(n_heavy, 1), **i32)
-    slot_begin = torch.empty(n_heavy + 1, **i32)
-    crow = torch.empty(max(n_chunks, 1), **i32)
-    cbeg = torch.empty(max(n_chunks, 1), dtype=torch.int64, device=dev)
-    cend = torch.empty(max(n_chunks, 1), dtype=torch.int64, device=dev)
-    w = ws.get(L.als_schedule_workspace_bytes(n_rows))
-    check(L.als_schedule_build(ptr(row_ptr), n_rows, chunk, n_light, n_heavy, n_chunks,
-                               ptr(light), ptr(heavy), ptr(slot_begin), ptr(crow), ptr(cbeg),
-                               ptr(cend), ptr(w), w.numel(), stream_ptr(dev)),
-          "als_schedule_build")
-    counts, nzs = (0,) * (DUAL_MAX_RATINGS + 1), (0,) * (DUAL_MAX_RATINGS + 1)
-    if n_light > 0:  # light rows are ordered by decreasing degree: the short ones are last
-        lr = light[:n_light].long()
-        deg = row_ptr[lr + 1] - row_ptr[lr]
-        short = deg[deg <= DUAL_MAX_RATINGS]
-        h = torch.bincount(short, minlength=DUAL_MAX_RATINGS + 1).to(torch.int64)
-        w = h * torch.arange(DUAL_MAX_RATINGS + 1, device=h.device)
-        counts = tuple(int(x) for x in torch.cumsum(h, 0).tolist())
-        nzs = tuple(int(x) for x in torch.cumsum(w, 0).tolist())
-    return RatingBlock(n_rows, nnz, row_ptr, col, val, chunk, n_light, n_heavy, n_chunks, light,
-                       heavy, slot_begin, crow, cbeg, cend, counts, nzs)
-
-
-# ---------------------------------------------------------------------------
-# K2/K3/K2b
-# ---------------------------------------------------------------------------
-def k_pad(rank: int) -> int:
-    return int(_lib.lib().als_k_pad(rank))
-
-
-def compute_yty(Y: torch.Tensor, n: int, rank: int, ws: Workspace) -> torch.Tensor:
-    """fp64 YtY (lower-packed, k_pad) of the first n rows of Y."""
-    L = _lib.lib()
-    kp = k_pad(rank)
-    out = torch.empty(kp * (kp + 1) // 2, dtype=torch.float64, device=Y.device)
-    w = ws.get(L.als_yty_workspace_bytes(n, rank))
-    check(L.als_yty(ptr(Y), n, Y.shape[1], rank, ptr(out), ptr(w), w.numel(),
-                    stream_ptr(Y.device)), "als_yty")
-    return out
-
-
-def solve_half(block: RatingBlock, Y: torch.Tensor, X: torch.Tensor, rank: int, reg: float,
-               implicit: bool, alpha: float, yty: Optional[torch.Tensor],
-               status: torch.Tensor, ws: Workspace, phases: int = PHASE_ALL,
-               ws_chunks: Optional[int] = None, dual: bool = True,
-               ws_rows: Optional[int] = None) -> None:
-    """One computeFactors pass: X[row] <- solve(A_row, b_row) for every row of `block`.
-    phases (PHASE_* bits, als_hip.h ALS_PHASE_*): PREP (max |Y|, split table), RSCALE
-    (rating scale), LAUNCH1 (chunk partials + primal light rows), DUAL (dual-path light
-    rows), LAUNCH2 (heavy rows), RESCUE (rows outside the split window); PHASE_ALL = all
-    in order.  ws_chunks / ws_rows: size the workspace for this many heavy-row chunks /
-    rows (blocks sharing one Y prep).
-    dual: explicit, reg > 0 — rows with <= dual_limit(rank) ratings are solved through
-    the equivalent n x n dual system (als_hip.h n_light_primal); False keeps every row
-    on the k x k normal equations."""
-    L = _lib.lib()
-    use_dual = dual and not implicit and reg > 0
-    n_primal = block.n_light - block.n_dual(rank) if use_dual else block.n_light
-    n_rows = max(block.n_light + block.n_heavy, ws_rows or 0)
-    w = ws.get(L.als_solve_workspace_bytes(rank, max(block.n_chunks, ws_chunks or 0), Y.shape[0],
-                                           n_rows), keep_scale=True)
-    key = (w.data_ptr(), w.numel())
-    if (phases & PHASE_RSCALE) and ws.shared_rating_scale and ws.rating_scale_key == key:
-        phases &= ~PHASE_RSCALE  # the rating scale word of this rating set is already in place
-        if phases == 0:
-            return
-    check(L.als_solve_half(ptr(block.row_ptr), ptr(block.col), ptr(block.val),
-                           ptr(block.light_rows), block.n_light, n_primal,
-                           ptr(block.heavy_rows),
-                           ptr(block.heavy_slot_begin), block.n_heavy, ptr(block.chunk_row),
-                           ptr(block.chunk_begin), ptr(block.chunk_end), block.n_chunks, 0, 0,
-                           ptr(Y), Y.shape[0], ptr(X), X.shape[1], rank, float(reg),
-                           int(bool(implicit)),
-                           float(alpha), ptr(yty), ptr(status), ptr(w), w.numel(), int(phases),
-                           stream_ptr(X.device)), "als_solve_half")
-    if (phases & PHASE_RSCALE) and ws.shared_rating_scale:
-        ws.rating_scale_key = key
-
-
-@dataclass
-class SplitSchedule:
-    """Two-segment schedule of one CSR block (ABI 6, the sharded engine's pipelined item
-    half-sweep).  Row r's ratings are [row_ptr[r], seg[r]) — the early segment, whose
-    source rows lie in the first n_src_early rows of Y (already gathered) — then
-    [seg[r], row_ptr[r+1]) (the late segment: the source chunk still arriving).  Each
-    segment is cut into <= chunk-rating tasks; every row goes through the heavy-row
-    path (fp32 task partials summed per row in fp64, then solved), early slots first.
-    Slots are numbered from slot_base (several blocks sharing one workspace and one Y
-    prep keep disjoint slot ranges: ShardedALS's item chunks)."""
-    n_src_early: int
-    rows: torch.Tensor          # int32 [n]: every row of the block, ascending
-    slot_begin: torch.Tensor    # int32 [n+1]: early slots of row r
-    slot_begin2: torch.Tensor   # int32 [n+1]: late slots of row r (after all early ones)
-    early: tuple                # (chunk_row, chunk_begin, chunk_end, n_tasks)
-    late: tuple
-    slot_base: int = 0          # first slot of this block's range in the workspace
-
-    @property
-    def n_slots(self) -> int:
-        """Slots of the workspace up to this block's last (slot_base included)."""
-        return self.slot_base + self.early[3] + self.late[3]
-
-
-def _segment_tasks(row_ids, begin, end, chunk: int, dev):
-    """<= chunk-rating tasks over the per-row ranges [begin[r], end[r])."""
-    ln = (end - begin).clamp(min=0)
-    cnt = (ln + chunk - 1) // chunk
-    n = int(cnt.sum())
-    slot_begin = torch.zeros(len(ln) + 1, dtype=torch.int64, device=dev)
-    slot_begin[1:] = torch.cumsum(cnt, 0)
-    if n == 0:
-        z32, z64 = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int64,
-                                                                              device=dev)
-        return slot_begin, (z32, z64, z64, 0)
-    crow = torch.repeat_interleave(torch.arange(len(ln), device=dev), cnt)
-    j = torch.arange(n, device=dev) - slot_begin[:-1][crow]
-    cb = begin[crow] + j * chunk
-    ce = torch.minimum(cb + chunk, end[crow])
-    return slot_begin, (row_ids[crow].to(torch.int32).contiguous(), cb.contiguous(),
-                        ce.contiguous(), n)
-
-
-def split_schedule(block: RatingBlock, seg: torch.Tensor, n_src_early: int,
-                   chunk: int = DEFAULT_CHUNK, slot_base: int = 0) -> SplitSchedule:
-    """The two-segment schedule of `block` (its rows' ratings ordered early-first, seg[r]
-    = end of row r's early segment), its slots numbered from slot_base."""
-    dev = block.row_ptr.device
-    n = block.n_rows
-    rp = block.row_ptr
-    seg = seg.to(dev, torch.int64)
-    rows = torch.arange(max(n, 1), dtype=torch.int32, device=dev)
-    sb1, early = _segment_tasks(rows[:n], rp[:-1], seg, chunk, dev)
-    sb2, late = _segment_tasks(rows[:n], seg, rp[1:], chunk, dev)
-    sb1 = sb1 + slot_base
-    sb2 = sb2 + early[3] + slot_base
-    return SplitSchedule(int(n_src_early), rows, sb1.to(torch.int32).contiguous(),
-                         sb2.to(torch.int32).contiguous(), early, late, int(slot_base))
-
-
-def solve_half_split(block: RatingBlock, sched: SplitSchedule, part: str, Y: torch.Tensor,
-                     X: torch.Tensor, rank: int, reg: float, implicit: bool, alpha: float,
-                     yty: Optional[torch.Tensor], status: torch.Tensor, ws: Workspace,
-                     prep: bool = True, ws_slots: Optional[int] = None,
-                     ws_rows: Optional[int] = None) -> None:
-    """One half of a two-segment half-sweep (ABI 6).  part "early": the early segments'
-    task partials from the first sched.n_src_early rows of Y (PREP over that prefix,
-    RSCALE, LAUNCH1), while the rest of Y may still be arriving; "late": the late
-    segments' partials from all of Y, then every row's slots summed and solved
-    (LAUNCH2) and the rescue (RESCUE, over the row's full ratings).  Both calls on
-    the same workspace, early first, in stream order.  Both pass slot_begin2 (it marks
-    the schedule two-segment: no heavy row is solved before its late partials).
-    prep=False: Y's prep for this part was done by an earlier call on this workspace
-    (blocks sharing one workspace with disjoint slot ranges, sized by ws_slots /
-    ws_rows for the largest: all early calls first, then all late ones)."""
-    L = _lib.lib()
-    n = block.n_rows
-    w = ws.get(L.als_solve_workspace_bytes(rank, max(sched.n_slots, ws_slots or 0), Y.shape[0],
-                                           max(n, ws_rows or 0)))
-    if part == "early":
-        crow, cb, ce, nt = sched.early
-        ph, slot0, n_src = PHASE_PREP | PHASE_RSCALE | PHASE_LAUNCH1, sched.slot_base, sched.n_src_early
-    elif part == "late":
-        crow, cb, ce, nt = sched.late
-        ph = PHASE_PREP | PHASE_RSCALE | PHASE_LAUNCH1 | PHASE_LAUNCH2 | PHASE_RESCUE
-        slot0, n_src = sched.slot_base + sched.early[3], Y.shape[0]
-    else:
-        raise ValueError(f"part must be 'early' or 'late', got {part!r}")
-    if not prep:
-        ph &= ~PHASE_PREP
-    sb2 = sched.slot_begin2
-    check(L.als_solve_half(ptr(block.row_ptr), ptr(block.col), ptr(block.val),
-                           ptr(block.light_rows), 0, 0, ptr(sched.rows), ptr(sched.slot_begin), n,
-                           ptr(crow), ptr(cb), ptr(ce), nt, ptr(sb2), slot0,
-                           ptr(Y), n_src, ptr(X), X.shape[1], rank, float(reg),
-                           int(bool(implicit)), float(alpha), ptr(yty), ptr(status), ptr(w),
-                           w.numel(), int(ph), stream_ptr(X.device)), "als_solve_half (split)")
-
-
-def fold_in_rows(row_ptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, Y: torch.Tensor,
-                 n_src: int, rank: int, reg: float, implicit: bool, alpha: float,
-                 yty: Optional[torch.Tensor], status: torch.Tensor, ws: Workspace):
-    """K7 (als_fold_in): the factor row of every ragged row (row_ptr int64 [n + 1], col int32
-    = dense rows of Y or -1, val f32: filters.ragged_rows) against the first n_src rows of
-    the fixed factors Y, in one launch.  Returns (X f32 [n, ld_for(rank)], n_used int32
-    [n]); a row without a used entry is zero.  status: device int32, row + 1 of a row whose
-    normal equations were not positive definite (raise_status)."""
-    L = _lib.lib()
-    n = int(row_ptr.numel()) - 1
-    dev = Y.device
-    X = torch.empty((n, ld_for(rank)), dtype=torch.float32, device=dev)
-    n_used = torch.empty(n, dtype=torch.int32, device=dev)
-    need = int(L.als_fold_in_workspace_bytes(n, rank))
-    w = ws.get(need) if need else None
-    check(L.als_fold_in(ptr(row_ptr), ptr(col), ptr(val), n, ptr(Y), int(n_src), Y.shape[1],
-                        rank, float(reg), int(bool(implicit)), float(alpha), ptr(yty), ptr(X),
-                        X.shape[1], ptr(n_used), ptr(status), ptr(w), w.numel() if need else 0,
-                        stream_ptr(dev)), "als_fold_in")
-    return X, n_used
-
-
-def nnls_rows(row_ptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, Y: torch.Tensor,
-              n_src: int, rank: int, reg: float, implicit: bool, alpha: float,
-              yty: Optional[torch.Tensor], ws: Workspace, chunk: int = DEFAULT_CHUNK,
-              X: Optional[torch.Tensor] = None, iters: bool = False):
-    """K13 (als_nnls_rows): fold_in_rows' rows solved under x >= 0 by Spark's NNLS solver —
-    the same ragged input (a RatingBlock's row_ptr / col / val included) and the same
-    normal equations, in three launches plus a device sort of the rows by degree.  chunk:
-    ratings per task of a longer row.  X: the f32 [n, ld] table to write (a half-sweep's
-    destination factors); None allocates [n, ld_for(rank)].  Returns (X, n_used int32 [n],
-    iterations int32 [n] or None).  No row fails and there is no status word."""
-    L = _lib.lib()
-    n = int(row_ptr.numel()) - 1
-    dev = Y.device
-    if X is None:
-        X = torch.empty((n, ld_for(rank)), dtype=torch.float32, device=dev)
-    n_used = torch.empty(n, dtype=torch.int32, device=dev)
-    it = torch.empty(n, dtype=torch.int32, device=dev) if iters else None
-    if n == 0:
-        return X, n_used, it
-    if col.numel() == 0:  # rows without a single entry: never read, but not null
-        col = torch.zeros(1, dtype=torch.int32, device=dev)
-        val = torch.zeros(1, dtype=torch.float32, device=dev)
-        nnz = 0
-    else:
-        nnz = int(col.numel())
-    need = int(L.als_nnls_workspace_bytes(n, nnz, rank, int(chunk)))
-    w = ws.get(need)
-    check(L.als_nnls_rows(ptr(row_ptr), ptr(col), ptr(val), n, ptr(Y), int(n_src), Y.shape[1],
-                          rank, float(reg), int(bool(implicit)), float(alpha), ptr(yty),
-                          int(chunk), ptr(X), X.shape[1], ptr(n_used), ptr(it), ptr(w),
-                          max(need, 256), stream_ptr(dev)), "als_nnls_rows")
-    return X, n_used, it
-
-
-EXPLAIN_MAX_TOP = 32
-
-
-def explain_rows(row_ptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, Y: torch.Tensor,
-                 n_src: int, rank: int, reg: float, implicit: bool, alpha: float,
-                 yty: Optional[torch.Tensor], tgt_ptr: torch.Tensor, tgt: torch.Tensor,
-                 top_n: int, status: torch.Tensor, ws: Workspace):
-    """K11 (als_explain): every score of the ragged rows (fold_in_rows' inputs) against their
-    ragged targets (tgt_ptr int64 [n + 1], tgt int32 = dense rows of Y or -1, tgt_ptr[n] ==
-    tgt.numel() == T) split into one contribution per rating, in one launch.  Returns
-    (score f32 [T], contrib_pos int32 [T, top_n] = entry offset inside the row or -1,
-    contrib f32 [T, top_n] descending, n_used int32 [n]).  status as fold_in_rows."""
-    L = _lib.lib()
-    n = int(row_ptr.numel()) - 1
-    T = int(tgt.numel())
-    dev = Y.device
-    if T == 0:  # the entry point wants addresses even when no slot is written
-        tgt = torch.full((1,), -1, dtype=torch.int32, device=dev)
-    score = torch.empty(max(T, 1), dtype=torch.float32, device=dev)
-    pos = torch.empty((max(T, 1), int(top_n)), dtype=torch.int32, device=dev)
-    contrib = torch.empty((max(T, 1), int(top_n)), dtype=torch.float32, device=dev)
-    n_used = torch.empty(n, dtype=torch.int32, device=dev)
-    if col.numel() == 0:  # rows without a single entry: never read, but not null
-        col = torch.zeros(1, dtype=torch.int32, device=dev)
-        val = torch.zeros(1, dtype=torch.float32, device=dev)
-    need = int(L.als_explain_workspace_bytes(n, rank))
-    w = ws.get(need) if need else None
-    check(L.als_explain(ptr(row_ptr), ptr(col), ptr(val), n, ptr(Y), int(n_src), Y.shape[1],
-                        rank, float(reg), int(bool(implicit)), float(alpha), ptr(yty),
-                        ptr(tgt_ptr), ptr(tgt), int(top_n), ptr(score), ptr(pos), ptr(contrib),
-                        ptr(n_used), ptr(status), ptr(w), w.numel() if need else 0,
-                        stream_ptr(dev)), "als_explain")
-    return score[:T], pos[:T], contrib[:T], n_used
-
-
-def group_pairs(rows: torch.Tensor, n_rows: int):
-    """Pairs' row index (int64, in [0, n_rows)) -> (order, tgt_ptr int64 [n_rows + 1]):
-    `order` lists the pairs grouped by row (stable: input order within a row), so pair
-    order[s] fills target slot s of als_explain and each row is factored once."""
-    rows = rows.reshape(-1).long()
-    order = torch.sort(rows, stable=True).indices
-    tgt_ptr = torch.zeros(int(n_rows) + 1, dtype=torch.int64, device=rows.device)
-    if rows.numel():
-        tgt_ptr[1:] = torch.cumsum(torch.bincount(rows, minlength=int(n_rows)), 0)
-    return order, tgt_ptr
-
-
-def raise_status(s: int, where: str = "") -> None:
-    """Raise for a non-zero solve status word: row + 1 of a failed Cholesky (Spark's
-    dppsv info > 0), or -1 when the fp64 rescue list overflowed (als_solve_half's
-    LAUNCH phases ran twice without the RESCUE phase between them)."""
-    if s < 0:
-        raise RuntimeError(f"als_solve_half rescue list overflow{where}: the LAUNCH phases ran "
-                           "again before the RESCUE phase consumed the list (unsolved rows)")
-    if s > 0:
-        raise RuntimeError(
-            f"Cholesky failed (non-positive pivot) for dense row {s - 1}{where}: the normal "
-            "equations are not positive definite (Spark raises from LAPACK dppsv here)")
-
-
-# ---------------------------------------------------------------------------
-# K4/K5
-# ---------------------------------------------------------------------------
-def predict_pairs(u: torch.Tensor, i: torch.Tensor, uidx: IdIndex, iidx: IdIndex,
-                  U: torch.Tensor, V: torch.Tensor, rank: int) -> torch.Tensor:
-    L = _lib.lib()
-    u, i = uidx.keys(u), iidx.keys(i)
-    out = torch.empty(u.numel(), dtype=torch.float64, device=U.device)
-    check(L.als_predict(ptr(u), ptr(i), u.numel(), ptr(uidx.map), uidx.id_space, ptr(iidx.map),
-                        iidx.id_space, ptr(U), ptr(V), U.shape[1], rank, ptr(out),
-                        stream_ptr(U.device)), "als_predict")
-    return out
-
-
-def rmse_pairs(u, i, r, uidx: IdIndex, iidx: IdIndex, U, V, rank: int, ws: Workspace):
-    """(sse, count) over pairs with both ids known (computeError's join)."""
-    L = _lib.lib()
-    u, i = uidx.keys(u), iidx.keys(i)
-    out = torch.empty(2, dtype=torch.float64, device=U.device)
-    w = ws.get(L.als_rmse_workspace_bytes(u.numel()))
-    check(L.als_rmse_partial(ptr(u), ptr(i), ptr(r), u.numel(), ptr(uidx.map), uidx.id_space,
-                             ptr(iidx.map), iidx.id_space, ptr(U), ptr(V), U.shape[1], rank,
-                             ptr(out), ptr(w), w.numel(), stream_ptr(U.device)),
-          "als_rmse_partial")
-    return out
-
-
-# K8 (als_regression_moments): the 8 doubles both forms write, in order
-MOMENT_NAMES = ("n", "mean_label", "M2_label", "mean_pred", "M2_pred", "sse", "sae", "n_dropped")
-
-
-def regression_moments_pairs(u, i, r, uidx: IdIndex, iidx: IdIndex, U, V, rank: int,
-                             ws: Workspace) -> torch.Tensor:
-    """K8, fused form: f64 [8] (MOMENT_NAMES) of label = r against the fp64 gather-dot of
-    K4 over the pairs with both ids known; the others are counted in n_dropped
-    (computeError's join, as rmse_pairs)."""
-    L = _lib.lib()
-    u, i = uidx.keys(u), iidx.keys(i)
-    out = torch.empty(8, dtype=torch.float64, device=U.device)
-    w = ws.get(L.als_regression_moments_workspace_bytes(u.numel()))
-    check(L.als_regression_moments(ptr(u), ptr(i), ptr(r), u.numel(), ptr(uidx.map),
-                                   uidx.id_space, ptr(iidx.map), iidx.id_space, ptr(U), ptr(V),
-                                   U.shape[1], rank, ptr(out), ptr(w), w.numel(),
-                                   stream_ptr(U.device)), "als_regression_moments")
-    return out
-
-
-def regression_moments_cols(label: torch.Tensor, pred: torch.Tensor, ws: Workspace
-                            ) -> torch.Tensor:
-    """K8, column form: f64 [8] (MOMENT_NAMES) of two contiguous fp64 device vectors of one
-    length; every row is used and a NaN in either makes the error-derived values NaN."""
-    L = _lib.lib()
-    if label.dtype != torch.float64 or pred.dtype != torch.float64:
-        raise ValueError("regression_moments_cols: label and pred must be float64 tensors")
-    if label.dim() != 1 or label.shape != pred.shape:
-        raise ValueError("regression_moments_cols: label and pred must be vectors of one length")
-    label, pred = label.contiguous(), pred.contiguous()
-    out = torch.empty(8, dtype=torch.float64, device=label.device)
-    w = ws.get(L.als_regression_moments_workspace_bytes(label.numel()))
-    check(L.als_regression_moments_cols(ptr(label), ptr(pred), label.numel(), ptr(out), ptr(w),
-                                        w.numel(), stream_ptr(label.device)),
-          "als_regression_moments_cols")
-    return out
-
-
-def regression_dict(moments, through_origin: bool = False) -> dict:
-    """Spark's RegressionMetrics (mllib/evaluation/RegressionMetrics.scala, upstream, not
-    vendored) from K8's 8 numbers (a host sequence in MOMENT_NAMES order); pure host fp64:
-      SSerr = sse, SStot = M2_label, SSy = M2_label + n mean_label^2,
-      SSreg = M2_pred + n (mean_pred - mean_label)^2
-      mse = SSerr / n, rmse = sqrt(mse), mae = sae / n, var = SSreg / n (explainedVariance),
-      r2 = 1 - SSerr / SStot, or 1 - SSerr / SSy with through_origin.
-    Also n, dropped (pairs the fused form left out), meanLabel and varLabel = M2_label / n
-    (population variance).  Divisions are IEEE: constant labels give r2 = -inf (sse > 0) or
-    NaN (sse = 0), and n = 0 gives NaN metrics, never an exception.
-    A constant prediction c has mse = varLabel + (meanLabel - c)^2, so the reference's
-    mean-rating baseline (RecommenderSystem.py:172-177: the training mean as every test
-    prediction) is sqrt(varLabel + (meanLabel - c)^2) of the test moments, with no second
-    pass over the data."""
-    n, ml, m2l, mp, m2p, sse, sae, drop = (np.float64(x) for x in moments)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        ss_tot = m2l + n * ml * ml if through_origin else m2l
-        ss_reg = m2p + n * (mp - ml) * (mp - ml)
-        mse = sse / n
-        out = {"mse": mse, "rmse": np.sqrt(mse), "mae": sae / n, "r2": 1.0 - sse / ss_tot,
-               "var": ss_reg / n, "meanLabel": ml if n > 0 else np.float64("nan"),
-               "varLabel": m2l / n}
-    out = {k: float(v) for k, v in out.items()}
-    out["n"] = int(n)
-    out["dropped"] = int(drop)
-    return out
-
-
-def ids_of(ids: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
-    """Ids of top-k dense rows.  A slot the kernel left empty (idx -1, score -inf: every
-    score of that query row NaN, from non-finite factors) keeps a placeholder id; the
-    callers drop slots whose score is not finite (valid_slots)."""
-    return ids[idx.long().clamp(min=0)]
-
-
-def topk_rows(Q: torch.Tensor, n_q: int, V: torch.Tensor, n_v: int, rank: int, top: int):
-    """(idx int32 [n_q, top], score f32 [n_q, top]); idx = dense V row, -1 past n_v."""
-    L = _lib.lib()
-    idx = torch.empty((n_q, top), dtype=torch.int32, device=Q.device)
-    sc = torch.empty((n_q, top), dtype=torch.float32, device=Q.device)
-    w = torch.empty(int(L.als_topk_workspace_bytes(n_q, n_v, rank, top)), dtype=torch.uint8,
-                    device=Q.device)
-    check(L.als_topk(ptr(Q), n_q, ptr(V), n_v, Q.shape[1], rank, top, ptr(idx), ptr(sc), ptr(w),
-                     w.numel(), stream_ptr(Q.device)), "als_topk")
-    return idx, sc
-
-
-def topk_rows_filtered(Q: torch.Tensor, n_q: int, V: torch.Tensor, n_v: int, rank: int, top: int,
-                       ex_begin, ex_end, ex_col, allow_bits):
-    """topk_rows over the admissible rows of V only (als_topk_filtered): query row r may
-    not list the V rows ex_col[ex_begin[r]:ex_end[r]] (int64 / int64 / int32 device
-    tensors, ascending within a row; all three None = no exclusions) nor a row whose bit
-    in allow_bits (int32 words of the uint32 mask; None = every row) is clear.  Slots
-    past a row's admissible rows hold idx -1, score -inf.  All four None: topk_rows."""
-    L = _lib.lib()
-    idx = torch.empty((n_q, top), dtype=torch.int32, device=Q.device)
-    sc = torch.empty((n_q, top), dtype=torch.float32, device=Q.device)
-    w = torch.empty(int(L.als_topk_workspace_bytes(n_q, n_v, rank, top)), dtype=torch.uint8,
-                    device=Q.device)
-    check(L.als_topk_filtered(ptr(Q), n_q, ptr(V), n_v, Q.shape[1], rank, top, ptr(ex_begin),
-                              ptr(ex_end), ptr(ex_col), ptr(allow_bits), ptr(idx), ptr(sc),
-                              ptr(w), w.numel(), stream_ptr(Q.device)), "als_topk_filtered")
-    return idx, sc
-
-
-SIMILAR_MAX_TOP = 256     # als_similar: neighbours per query
-SIMILAR_MAX_SLICES = 4096
-# Distinct query rows from which ALSCore.similar leaves the table sweep (K12, one pass over
-# the table per 16 queries) for the unit copy + K5 route (one set-up, then every query in
-# one sweep).  Set from the measured crossover: DESIGN.md section K12,
-# profiles/k12_similar_cost.json.
-SIMILAR_SWEEP_MIN_ROWS = 256
-
-
-def similar_rows(Q: torch.Tensor, n_q: int, T: torch.Tensor, n: int, rank: int, top: int,
-                 self_rows, allow_bits, slices: int = 0):
-    """K12 (als_similar): the `top` rows of the table T [n, ld] nearest in cosine to each of
-    the n_q query vectors Q [n_q, ldq], from the raw fp32 rows.  self_rows (int32 [n_q] or
-    None): the table row a query must never list, -1 for none; allow_bits: the
-    filters.pack_allow_bits mask or None; slices: 0 = auto (tests pin it).  Returns (idx
-    int32 [n_q, top], score f32 [n_q, top]), score descending, ties by ascending row;
-    empty slots idx -1, score -inf."""
-    n_q, n, rank, top, slices = int(n_q), int(n), int(rank), int(top), int(slices)
-    if not 1 <= top <= SIMILAR_MAX_TOP:
-        raise ValueError(f"top must be in [1, {SIMILAR_MAX_TOP}], got {top}")
-    if not 1 <= rank <= MAX_RANK:
-        raise ValueError(f"rank must be in [1, {MAX_RANK}], got {rank}")
-    if not 0 <= slices <= SIMILAR_MAX_SLICES:
-        raise ValueError(f"slices must be in [0, {SIMILAR_MAX_SLICES}] (0 = auto), got {slices}")
-    if n_q < 0 or n < 0:
-        raise ValueError("n_q and n must be >= 0")
-    L = _lib.lib()
-    dev = Q.device
-    idx = torch.empty((n_q, top), dtype=torch.int32, device=dev)
-    sc = torch.empty((n_q, top), dtype=torch.float32, device=dev)
-    w = torch.empty(max(int(L.als_similar_workspace_bytes(n, min(n_q, 16), top, slices)), 256),
-                    dtype=torch.uint8, device=dev)
-    check(L.als_similar(ptr(T), n, T.shape[1], rank, ptr(Q), n_q, Q.shape[1], ptr(self_rows),
-                        ptr(allow_bits), top, slices, ptr(idx), ptr(sc), ptr(w), w.numel(),
-                        stream_ptr(dev)), "als_similar")
-    return idx, sc
-
-
-def unit_rows(T: torch.Tensor, n: int, rank: int, allow_bits=None):
-    """als_similar_unit_rows: (unit-norm fp32 copy of T's first n rows, allow mask, valid
-    int32 [n]).  The mask is a copy of allow_bits (or all ones) with the bit of every row
-    that can be nobody's neighbour (zero norm, NaN, Inf) cleared, in the same launch; such
-    rows are zeros in the copy and 0 in valid."""
-    L = _lib.lib()
-    n = int(n)
-    dev = T.device
-    out = torch.empty((n, T.shape[1]), dtype=torch.float32, device=dev)
-    valid = torch.empty(n, dtype=torch.int32, device=dev)
-    if allow_bits is None:
-        bits = torch.full((max((n + 31) // 32, 1),), -1, dtype=torch.int32, device=dev)
-    else:
-        bits = allow_bits.clone()
-    check(L.als_similar_unit_rows(ptr(T), n, T.shape[1], int(rank), ptr(out), ptr(bits),
-                                  ptr(valid), stream_ptr(dev)), "als_similar_unit_rows")
-    return out, bits, valid
-
-
-def similar_rows_unit(rows: Optional[torch.Tensor], T: torch.Tensor, n: int, rank: int, top: int,
-                      allow_bits=None):
-    """The many-query route to similar_rows' contract, built from K5: a unit-norm copy of
-    the table (unit_rows) is both Q and V of topk_rows_filtered, each query excludes its own
-    row through the exclusion arrays (begin = r, end = r + 1 into col = arange(n)), and the
-    lists of query rows without a direction (zero norm, NaN, Inf) are blanked afterwards —
-    K5 would list the first rows by index at score 0.  rows: dense table rows (int64) that
-    are the queries, None = every row.  Scores agree with similar_rows within 1e-5; pairs
-    closer than that may be ordered differently by the two routes."""
-    if not 1 <= int(top) <= SIMILAR_MAX_TOP:
-        raise ValueError(f"top must be in [1, {SIMILAR_MAX_TOP}], got {top}")
-    n = int(n)
-    dev = T.device
-    Tn, bits, valid = unit_rows(T, n, rank, allow_bits)
-    col = torch.arange(max(n, 1), dtype=torch.int32, device=dev)
-    if rows is None:
-        Qn, beg, ok = Tn, torch.arange(n, dtype=torch.int64, device=dev), valid
-    else:
-        rows = rows.long()
-        Qn, beg, ok = Tn.index_select(0, rows).contiguous(), rows.contiguous(), valid[rows]
-    idx, sc = topk_rows_filtered(Qn, int(beg.numel()), Tn, n, rank, int(top), beg,
-                                 (beg + 1).contiguous(), col, bits)
-    dead = ok == 0
-    idx[dead] = -1
-    sc[dead] = float("-inf")
-    return idx, sc
-
-
-DIVERSIFY_MAX_POOL = 256  # als_diversify / als_list_similarity: slots per row
-# Pool arrays (idx int32 + score f32 per slot) ALSCore.recommend_diverse keeps alive at once.
-DIVERSIFY_POOL_BYTES = 1 << 30
-
-
-def _check_lists(idx: torch.Tensor, n_v: int, rank: int) -> None:
-    if idx.dim() != 2:
-        raise ValueError(f"idx must be [n_q, m], got shape {tuple(idx.shape)}")
-    if not 1 <= int(idx.shape[1]) <= DIVERSIFY_MAX_POOL:
-        raise ValueError(f"lists must have 1 to {DIVERSIFY_MAX_POOL} slots, got {idx.shape[1]}")
-    if not 1 <= int(rank) <= MAX_RANK:
-        raise ValueError(f"rank must be in [1, {MAX_RANK}], got {rank}")
-    if int(n_v) < 0:
-        raise ValueError("n_v must be >= 0")
-
-
-def diversify_rows(idx: torch.Tensor, sc: torch.Tensor, V: torch.Tensor, n_v: int, rank: int,
-                   top: int, lam: float):
-    """K14 (als_diversify): maximal-marginal-relevance re-ranking of each row's candidate
-    pool.  idx int32 [n_q, m] / sc f32 [n_q, m]: the pool as topk_rows / topk_rows_filtered
-    return it (dense rows of V [n_v, ld], open slots -1 / -inf), m <= DIVERSIFY_MAX_POOL;
-    1 <= top <= m; lam in [0, 1] (1 = pure relevance, 0 = pure diversity after the first
-    pick; rounded to fp32 on its way to the library).  Returns (idx int32 [n_q, top], score
-    f32 [n_q, top], ils f64 [n_q]): the picks in pick order with their original scores, open
-    slots -1 / -inf, and each list's mean pairwise cosine (NaN under two picks).  The
-    contract is in include/als_hip.h."""
-    _check_lists(idx, n_v, rank)
-    if tuple(sc.shape) != tuple(idx.shape):
-        raise ValueError(f"idx {tuple(idx.shape)} and sc {tuple(sc.shape)} must have one shape")
-    n_q, m = int(idx.shape[0]), int(idx.shape[1])
-    top, lam = int(top), float(lam)
-    if not 1 <= top <= m:
-        raise ValueError(f"top must be in [1, pool = {m}], got {top}")
-    if not 0.0 <= lam <= 1.0:   # (a NaN fails both comparisons)
-        raise ValueError(f"lam must be in [0, 1], got {lam}")
-    L = _lib.lib()
-    dev = V.device
-    idx = idx.to(torch.int32).contiguous()
-    sc = sc.to(torch.float32).contiguous()
-    out_i = torch.empty((n_q, top), dtype=torch.int32, device=dev)
-    out_s = torch.empty((n_q, top), dtype=torch.float32, device=dev)
-    ils = torch.empty(n_q, dtype=torch.float64, device=dev)
-    check(L.als_diversify(ptr(V), int(n_v), V.shape[1], int(rank), ptr(idx), ptr(sc), n_q, m, top,
-                          lam, ptr(out_i), ptr(out_s), ptr(ils), stream_ptr(dev)),
-          "als_diversify")
-    return out_i, out_s, ils
-
-
-def list_similarity_rows(idx: torch.Tensor, V: torch.Tensor, n_v: int, rank: int):
-    """K14 (als_list_similarity): ils f64 [n_q], the mean cosine over the unordered pairs of
-    the slots of idx int32 [n_q, m] (m <= DIVERSIFY_MAX_POOL) that name a row of V [n_v, ld]
-    (0 <= idx < n_v; anything else, such as the -1 of an open slot, is skipped); NaN with
-    fewer than two.  A row of V without a direction (zero norm, NaN, Inf) counts with
-    cosine 0."""
-    _check_lists(idx, n_v, rank)
-    L = _lib.lib()
-    dev = V.device
-    idx = idx.to(torch.int32).contiguous()
-    n_q, m = int(idx.shape[0]), int(idx.shape[1])
-    out = torch.empty(n_q, dtype=torch.float64, device=dev)
-    check(L.als_list_similarity(ptr(V), int(n_v), V.shape[1], int(rank), ptr(idx), n_q, m,
-                                ptr(out), stream_ptr(dev)), "als_list_similarity")
-    return out
-
-
-# ---------------------------------------------------------------------------
-# K15: the lists of all rows together (exposure, concentration, popularity)
-# ---------------------------------------------------------------------------
-LIST_MAX_AT = 256  # als_list_exposure / als_list_novelty: list positions read per row
-LIST_METRIC_FIELDS = ("coverage", "gini", "entropy", "effectiveItems", "personalization",
-                      "topItemShare", "novelty", "averagePopularity", "longTailShare", "lists",
-                      "entries", "skipped")
-
-
-def _list_rows_args(idx, at, who: str):
-    """(n_q, idx_ld, at) of a list matrix for the K15 calls; raises before the library is
-    touched."""
-    if (not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32 or idx.dim() != 2
-            or (idx.shape[1] > 1 and idx.stride(1) != 1)):
-        raise ValueError(f"{who}: idx must be an int32 [n_q, width] tensor with unit stride "
-                         "along a row")
-    at = int(at)
-    if not 1 <= at <= LIST_MAX_AT:
-        raise ValueError(f"{who}: at must be in [1, {LIST_MAX_AT}], got {at}")
-    if idx.shape[1] < at:
-        raise ValueError(f"{who}: lists of width {idx.shape[1]} < at = {at}")
-    n_q = int(idx.shape[0])
-    ld = int(idx.stride(0)) if n_q > 1 else int(idx.shape[1])  # one row: any stride
-    return n_q, ld, at
-
-
-def list_exposure_window() -> int:
-    """Rows per LDS counter window of als_list_exposure (0: the kernel keeps none)."""
-    return int(_lib.lib().als_list_exposure_window())
-
-
-def list_exposure_rows(idx: torch.Tensor, at: int, n_v: int, allow_bits=None, *, counts=None,
-                       skipped=None):
-    """K15 (als_list_exposure) over the lists idx (int32 [n_q, >= at], dense rows): how often
-    each of the n_v rows is named in the first `at` positions.  An entry outside [0, n_v) —
-    the -1 of an open slot — or with its bit clear in allow_bits (filters.pack_allow_bits;
-    None: every row) is skipped.  Returns (counts int32 [n_v], skipped int64 [1]), both on
-    the device; given `counts` (and `skipped`) from an earlier call, the new lists are added
-    to them, so lists can be fed in chunks.  Integer adds: exact, and the same bits every
-    run."""
-    n_q, ld, at = _list_rows_args(idx, at, "list_exposure_rows")
-    n_v = int(n_v)
-    if n_v < 0:
-        raise ValueError("list_exposure_rows: n_v must be >= 0")
-    accumulate = counts is not None
-    if accumulate and (counts.dtype != torch.int32 or counts.numel() != n_v
-                       or not counts.is_contiguous()):
-        raise ValueError(f"list_exposure_rows: counts must be a contiguous int32 [{n_v}] tensor")
-    if skipped is not None and not accumulate:
-        raise ValueError("list_exposure_rows: skipped= continues an earlier call: pass its "
-                         "counts too")
-    L = _lib.lib()
-    dev = idx.device
-    if counts is None:
-        counts = torch.empty(n_v, dtype=torch.int32, device=dev)
-    if skipped is None:
-        skipped = torch.zeros(1, dtype=torch.int64, device=dev)
-    check(L.als_list_exposure(ptr(idx), n_q, ld, at, n_v, ptr(allow_bits), int(accumulate),
-                              ptr(counts), ptr(skipped), stream_ptr(dev)), "als_list_exposure")
-    return counts, skipped
-
-
-def list_concentration(counts: torch.Tensor, n_v: int, allow_bits, n_lists: int, at: int,
-                       ws: Workspace) -> torch.Tensor:
-    """K15 (als_list_concentration): f64 [7] on the device = catalogue rows, rows listed, total,
-    Gini index, Shannon entropy (bits), pair overlap sum c (c - 1) / 2, largest count, over the
-    counts of the catalogue rows (every row, or those set in allow_bits).  Gini and entropy are
-    NaN when nothing is listed."""
-    n_v = int(n_v)
-    if counts.dtype != torch.int32 or counts.numel() != n_v or not counts.is_contiguous():
-        raise ValueError(f"list_concentration: counts must be a contiguous int32 [{n_v}] tensor")
-    if not 1 <= int(at) <= LIST_MAX_AT:
-        raise ValueError(f"list_concentration: at must be in [1, {LIST_MAX_AT}], got {at}")
-    L = _lib.lib()
-    dev = counts.device
-    out = torch.empty(7, dtype=torch.float64, device=dev)
-    w = ws.get(L.als_list_concentration_scratch_bytes(n_v))
-    check(L.als_list_concentration(ptr(counts), n_v, ptr(allow_bits), int(n_lists), int(at),
-                                   ptr(out), ptr(w), w.numel(), stream_ptr(dev)),
-          "als_list_concentration")
-    return out
-
-
-def list_novelty_rows(idx: torch.Tensor, at: int, n_v: int, pop: torch.Tensor, n_pop: int,
-                      ws: Workspace, allow_bits=None, tail_bits=None, per_row: bool = False):
-    """K15 (als_list_novelty) over the lists idx (as list_exposure_rows): pop int32 [n_v] = how
-    often each row was rated, n_pop = rows of the listing side, tail_bits = the long-tail rows
-    (the form of allow_bits; None: no long-tail share).  Returns (sums f64 [7] = sum of row
-    novelty (mean log2(n_pop / pop) over the entries with pop > 0), rows with one, sum of row
-    mean popularity, rows with a valid entry, sum of row long-tail share, valid entries, skipped
-    entries; per-row f64 [n_q, 3] = novelty, mean popularity, long-tail share with NaN where
-    undefined, or None)."""
-    n_q, ld, at = _list_rows_args(idx, at, "list_novelty_rows")
-    n_v = int(n_v)
-    if pop.dtype != torch.int32 or pop.numel() != n_v or not pop.is_contiguous():
-        raise ValueError(f"list_novelty_rows: pop must be a contiguous int32 [{n_v}] tensor")
-    if int(n_pop) < 1:
-        raise ValueError(f"list_novelty_rows: n_pop must be >= 1, got {n_pop}")
-    L = _lib.lib()
-    dev = idx.device
-    out = torch.empty(7, dtype=torch.float64, device=dev)
-    rows = torch.empty((n_q, 3), dtype=torch.float64, device=dev) if per_row else None
-    w = ws.get(L.als_list_novelty_scratch_bytes(n_q))
-    check(L.als_list_novelty(ptr(idx), n_q, ld, at, n_v, ptr(allow_bits), ptr(pop), int(n_pop),
-                             ptr(tail_bits), ptr(out), ptr(rows), ptr(w), w.numel(),
-                             stream_ptr(dev)), "als_list_novelty")
-    return out, rows
-
-
-def long_tail_bits(pop: torch.Tensor, n_v: int, head_fraction: float, cat_rows=None):
-    """The long tail as a bit mask (filters.pack_allow_bits): every catalogue row (cat_rows,
-    ascending dense rows; None: all n_v) outside the floor(head_fraction * n) most-rated ones,
-    n = the catalogue's size.  Rows rated equally often at the cut go to the head by ascending
-    row (one stable torch.sort)."""
-    head_fraction = float(head_fraction)
-    if not 0.0 < head_fraction < 1.0:
-        raise ValueError(f"head_fraction must be inside (0, 1), got {head_fraction}")
-    n_v = int(n_v)
-    if cat_rows is None:
-        cat_rows = torch.arange(n_v, device=pop.device)
-    cat_rows = cat_rows.long()
-    n_head = int(math.floor(head_fraction * int(cat_rows.numel())))
-    order = torch.sort(pop[cat_rows].long(), descending=True, stable=True).indices
-    return _filters.pack_allow_bits(cat_rows[order[n_head:]], n_v)
-
-
-def list_metrics_dict(conc, nov, n_lists: int, at: int, skipped: int = 0,
-                      tail: bool = True) -> dict:
-    """K15's raw sums (host lists: als_list_concentration's 7, als_list_novelty's 7 or None
-    when no popularity is known) as the beyond-accuracy measures of n_lists lists of `at`
-    slots:
-      coverage          catalogue rows listed at least once / catalogue rows
-      gini, entropy     of the exposure counts (entropy in bits); effectiveItems = 2 ** entropy
-      personalization   1 - mean overlap of two lists = 1 - pairs / (C(n_lists, 2) at);
-                        NaN under two lists
-      topItemShare      the share of the lists that name the most listed row
-      novelty           mean over the lists of the mean log2(n_pop / popularity)
-      averagePopularity mean over the lists of the mean popularity of what they name
-      longTailShare     mean over the lists of the share of long-tail rows
-      lists, entries (valid ones), skipped (open slots, unknown ids, rows off the catalogue)
-    The three popularity fields are NaN without `nov` (longTailShare also with tail=False)."""
-    nan = float("nan")
-
-    def ratio(a, b):
-        return a / b if b > 0 else nan
-    n_lists, at = int(n_lists), int(at)
-    pairs = n_lists * (n_lists - 1) // 2
-    entropy = conc[4]
-    out = {"coverage": ratio(conc[1], conc[0]), "gini": conc[3], "entropy": entropy,
-           "effectiveItems": 2.0 ** entropy if entropy == entropy else nan,
-           "personalization": 1.0 - conc[5] / (pairs * at) if pairs > 0 else nan,
-           "topItemShare": ratio(conc[6], n_lists),
-           "novelty": nan, "averagePopularity": nan, "longTailShare": nan,
-           "lists": n_lists, "entries": int(conc[2]), "skipped": int(skipped)}
-    if nov is not None:
-        out["novelty"] = ratio(nov[0], nov[1])
-        out["averagePopularity"] = ratio(nov[2], nov[3])
-        if tail:
-            out["longTailShare"] = ratio(nov[4], nov[3])
-        out["skipped"] = int(nov[6])
-    return out
-
-
-def list_metrics_rows(rows: torch.Tensor, at: int, n_v: int, ws: Workspace, *, allow_bits=None,
-                      cat_rows=None, pop=None, n_pop=None, head_fraction: float = 0.2,
-                      per_row: bool = False):
-    """The three K15 calls over one list matrix (int32 [n, >= at] dense rows) and
-    list_metrics_dict of their sums.  allow_bits / cat_rows: the catalogue as a mask and as
-    ascending rows (both None: all n_v rows).  pop / n_pop as list_novelty_rows; without pop
-    the popularity fields are NaN.  Returns (dict, per-row f64 [n, 3] or None)."""
-    n, _, at = _list_rows_args(rows, at, "list_metrics_rows")
-    head_fraction = float(head_fraction)
-    if not 0.0 < head_fraction < 1.0:
-        raise ValueError(f"head_fraction must be inside (0, 1), got {head_fraction}")
-    counts, skipped = list_exposure_rows(rows, at, n_v, allow_bits)
-    conc = list_concentration(counts, n_v, allow_bits, n, at, ws)
-    nov = pr = None
-    if pop is not None:
-        tail = long_tail_bits(pop, n_v, head_fraction, cat_rows)
-        nov, pr = list_novelty_rows(rows, at, n_v, pop, n_pop, ws, allow_bits, tail, per_row)
-        nov = nov.tolist()
-    elif per_row:
-        pr = torch.full((n, 3), float("nan"), dtype=torch.float64, device=rows.device)
-    return list_metrics_dict(conc.tolist(), nov, n, at, int(skipped.item())), pr
-
-
-MAX_RANK_AT = 256  # als_rank_metrics: list positions scored per row
-
-
-def rank_metrics_rows(idx: torch.Tensor, at: int, begin, end, col, ws: Workspace,
-                      per_row: bool = False):
-    """K6 over the lists idx (int32 [n_q, >= at], dense rows, negative = empty slot)
-    against the relevant sets col[begin[r]:end[r]] (strictly ascending: filters.
-    relevance_lists).  Returns (sums f64 [6] = sum precision, sum recall, sum AP, sum
-    NDCG, rows with a relevant set, rows with a hit; per-row f64 [n_q, 4] or None)."""
-    L = _lib.lib()
-    if idx.dtype != torch.int32 or idx.dim() != 2 or (idx.shape[1] > 1 and idx.stride(1) != 1):
-        raise ValueError("rank_metrics_rows: idx must be an int32 [n_q, width] tensor with "
-                         "unit stride along a row")
-    if idx.shape[1] < int(at):
-        raise ValueError(f"rank_metrics_rows: lists of width {idx.shape[1]} < at = {at}")
-    n_q = int(idx.shape[0])
-    out = torch.empty(6, dtype=torch.float64, device=idx.device)
-    rows = torch.empty((n_q, 4), dtype=torch.float64, device=idx.device) if per_row else None
-    w = ws.get(L.als_rank_metrics_workspace_bytes(n_q))
-    ld = int(idx.stride(0)) if n_q > 1 else int(idx.shape[1])  # one row: any stride
-    check(L.als_rank_metrics(ptr(idx), n_q, ld, int(at),
-                             ptr(begin), ptr(end), ptr(col), ptr(out), ptr(rows), ptr(w),
-                             w.numel(), stream_ptr(idx.device)), "als_rank_metrics")
-    return out, rows
-
-
-def rank_metrics_dict(sums, rows: int) -> dict:
-    """The means over `rows` query rows of K6's sums (host list of 6); NaN when rows == 0."""
-    def mean(x):
-        return x / rows if rows > 0 else float("nan")
-    return {"precision": mean(sums[0]), "recall": mean(sums[1]), "map": mean(sums[2]),
-            "ndcg": mean(sums[3]), "hitRate": mean(sums[5]), "rows": int(rows)}
-
-
-FULL_RANK_SUMS = ("sum_w_pr", "sum_w", "sum_row_pr", "sum_auc", "auc_rows", "sum_rr", "rr_rows",
-                  "rows", "pairs", "inadmissible", "pr_rows")   # als_full_rank_metrics' sums_out
-
-
-def rank_positions_table() -> int:
-    """Relevant entries one workgroup of K9 ranks per sweep of V (its LDS threshold table)."""
-    return int(_lib.lib().als_rank_positions_table())
-
-
-def rank_positions_rows(Q: torch.Tensor, n_q: int, V: torch.Tensor, n_v: int, rank: int,
-                        rel_begin, rel_end, rel_col, ex_begin=None, ex_end=None, ex_col=None,
-                        allow_bits=None):
-    """K9's sweep (als_rank_positions): for every relevant entry rel_col[e] of query row r
-    (rel_begin / rel_end / rel_col as filters.relevance_lists gives them) the admissible rows
-    of V that score strictly higher and equal, and per query row the admissible rows.  The
-    ex_* / allow_bits filter is topk_rows_filtered's.  Returns (above int32 [len(rel_col)],
-    tied int32, n_adm int32 [n_q]); above = tied = -1 for an entry that is itself
-    inadmissible or scores NaN, and for entries of rel_col no row points at."""
-    L = _lib.lib()
-    dev = Q.device
-    above = torch.full((max(int(rel_col.numel()), 1),), -1, dtype=torch.int32, device=dev)
-    tied = torch.full_like(above, -1)
-    n_adm = torch.zeros(max(int(n_q), 1), dtype=torch.int32, device=dev)
-    check(L.als_rank_positions(ptr(Q), int(n_q), ptr(V), int(n_v), Q.shape[1], int(rank),
-                               ptr(rel_begin), ptr(rel_end), ptr(rel_col), ptr(ex_begin),
-                               ptr(ex_end), ptr(ex_col), ptr(allow_bits), ptr(above), ptr(tied),
-                               ptr(n_adm), 0, 0, stream_ptr(dev)), "als_rank_positions")
-    return above[:rel_col.numel()], tied[:rel_col.numel()], n_adm[:int(n_q)]
-
-
-def full_rank_sums_rows(above, tied, n_adm, rel_begin, rel_end, ws: Workspace, weights=None,
-                        per_row: bool = False):
-    """K9's reduction (als_full_rank_metrics) of rank_positions_rows' counts: (sums f64 [11] in
-    FULL_RANK_SUMS order; per-row f64 [n_q, 3] = mean percentile rank, AUC, RR, or None)."""
-    L = _lib.lib()
-    n_q = int(n_adm.numel())
-    dev = n_adm.device
-    out = torch.empty(len(FULL_RANK_SUMS), dtype=torch.float64, device=dev)
-    rows = torch.empty((n_q, 3), dtype=torch.float64, device=dev) if per_row else None
-    w = ws.get(L.als_full_rank_workspace_bytes(n_q))
-    check(L.als_full_rank_metrics(ptr(above), ptr(tied), ptr(n_adm), n_q, ptr(rel_begin),
-                                  ptr(rel_end), ptr(weights), ptr(out), ptr(rows), ptr(w),
-                                  w.numel(), stream_ptr(dev)), "als_full_rank_metrics")
-    return out, rows
-
-
-def full_rank_dict(sums) -> dict:
-    """The full-ranking metrics from K9's sums (host list of 11, FULL_RANK_SUMS order).
-    expectedPercentileRank = sum w pr / sum w over the valid pairs (Hu, Koren & Volinsky's
-    measure when w is the held-out rating; 0.5 = random, lower is better),
-    meanPercentileRank = mean of the rows' mean percentile rank, auc / mrr = means of the
-    row AUC / reciprocal rank over the rows where each is defined.  A mean with an empty
-    denominator is NaN.  rows = query rows with a valid pair, pairs = valid pairs,
-    inadmissible = pairs left out because the filter excludes the item itself or its score
-    is NaN."""
-    s = [float(x) for x in sums]
-    if len(s) != len(FULL_RANK_SUMS):
-        raise ValueError(f"full_rank_dict: {len(FULL_RANK_SUMS)} sums expected, got {len(s)}")
-
-    def ratio(a, b):
-        return a / b if b > 0 else float("nan")
-    return {"expectedPercentileRank": ratio(s[0], s[1]), "meanPercentileRank": ratio(s[2], s[10]),
-            "auc": ratio(s[3], s[4]), "mrr": ratio(s[5], s[6]), "rows": int(s[7]),
-            "pairs": int(s[8]), "inadmissible": int(s[9])}
-
-
-OBJECTIVE_SIDE = ("data", "scale", "reg", "n", "n_positive")   # als_objective_side's out
-
-
-def objective_span() -> int:
-    """Ratings one workgroup of K10's rating pass owns (als_objective_span)."""
-    return int(_lib.lib().als_objective_span())
-
-
-def objective_side(block: RatingBlock, X: torch.Tensor, Y: Optional[torch.Tensor], n_cols: int,
-                   rank: int, implicit: bool, alpha: float, ws: Workspace,
-                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """K10's rating pass over one CSR side (als_objective_side): f64 [5] in OBJECTIVE_SIDE
-    order — the data terms of the side's ratings against X (its rows) and Y (its columns),
-    their absolute sum, sum_row n_row |x_row|^2 (not yet times regParam) and the two counts.
-    Y None: the regulariser and the counts only.  out: a device f64 [5] to write into."""
-    L = _lib.lib()
-    if out is None:
-        out = torch.empty(len(OBJECTIVE_SIDE), dtype=torch.float64, device=X.device)
-    w = ws.get(L.als_objective_workspace_bytes(block.nnz, block.n_rows, rank))
-    check(L.als_objective_side(ptr(block.row_ptr), ptr(block.col), ptr(block.val), block.nnz,
-                               block.n_rows, int(n_cols), ptr(X), ptr(Y), X.shape[1], rank,
-                               int(bool(implicit)), float(alpha), ptr(out), ptr(w), w.numel(),
-                               stream_ptr(X.device)), "als_objective_side")
-    return out
-
-
-def gram_dot(A: torch.Tensor, n_a: int, B: torch.Tensor, n_b: int, rank: int, ws: Workspace,
-             grams: bool = False, out: Optional[torch.Tensor] = None):
-    """K10's <A^T A, B^T B>_F over the first n_a / n_b rows of two fp32 tables of one leading
-    dimension, the Grams formed in fp64 (als_gram_dot_f64): a device f64 [1]; with grams=True
-    (dot, A^T A, B^T B), the Grams f64 [rank, rank]."""
-    L = _lib.lib()
-    if A.shape[1] != B.shape[1]:
-        raise ValueError("gram_dot: the two tables must share a leading dimension")
-    dev = A.device
-    if out is None:
-        out = torch.empty(1, dtype=torch.float64, device=dev)
-    ga = torch.empty((rank, rank), dtype=torch.float64, device=dev) if grams else None
-    gb = torch.empty((rank, rank), dtype=torch.float64, device=dev) if grams else None
-    w = ws.get(L.als_objective_workspace_bytes(0, max(int(n_a), int(n_b)), rank))
-    check(L.als_gram_dot_f64(ptr(A), int(n_a), ptr(B), int(n_b), A.shape[1], rank, ptr(out),
-                             ptr(ga), ptr(gb), ptr(w), w.numel(), stream_ptr(dev)),
-          "als_gram_dot_f64")
-    return (out, ga, gb) if grams else out
-
-
-# ---------------------------------------------------------------------------
-# K16: rating statistics and bias baselines
-# ---------------------------------------------------------------------------
-RATING_MOMENTS = ("n", "sum", "M2", "min", "max")   # als_row_moments' columns, and its total
-BASELINE_METHODS = ("global", "item", "user", "bias")
-
-
-def rating_stats_task() -> int:
-    """Ratings per task of a long row in K16's sweep (als_rating_stats_task)."""
-    return int(_lib.lib().als_rating_stats_task())
-
-
-def rating_stats_group_rows() -> int:
-    """Rows one workgroup of K16's sweep owns (als_rating_stats_group_rows)."""
-    return int(_lib.lib().als_rating_stats_group_rows())
-
-
-def _host_f64(x) -> ctypes.c_double:
-    """A host double the library reads through its address before the call returns."""
-    return ctypes.c_double(float(x))
-
-
-def row_moments(block_or_csr, n_cols: int, ws: Workspace, other: Optional[torch.Tensor] = None,
-                offset: float = 0.0, moments: Optional[torch.Tensor] = None,
-                total: Optional[torch.Tensor] = None):
-    """K16's sweep over one CSR side (als_row_moments): a RatingBlock, or (row_ptr int64
-    [n + 1], col int32, val fp32) device tensors.  Terms e = val - offset - other[col] (other:
-    f64 [n_cols] on the device, or None).  Returns (moments f64 [n_rows, 5], total f64 [5]),
-    columns in RATING_MOMENTS order; a row without ratings has n = sum = M2 = 0 and NaN min /
-    max.  moments / total: device tensors to write into."""
-    L = _lib.lib()
-    if isinstance(block_or_csr, RatingBlock):
-        row_ptr, col, val = block_or_csr.row_ptr, block_or_csr.col, block_or_csr.val
-    else:
-        row_ptr, col, val = block_or_csr
-    dev = row_ptr.device
-    n_rows, nnz = int(row_ptr.numel()) - 1, int(val.numel())
-    if n_rows < 0 or int(col.numel()) != nnz:
-        raise ValueError("row_moments: row_ptr needs n_rows + 1 entries and col / val one length")
-    if other is not None:
-        if other.dtype != torch.float64 or other.numel() != int(n_cols):
-            raise ValueError("row_moments: other must be a float64 table of n_cols entries")
-        other = other.contiguous()
-    if moments is None:
-        moments = torch.empty((n_rows, len(RATING_MOMENTS)), dtype=torch.float64, device=dev)
-    if total is None:
-        total = torch.empty(len(RATING_MOMENTS), dtype=torch.float64, device=dev)
-    off = _host_f64(offset)
-    w = ws.get(L.als_rating_stats_scratch_bytes(nnz, n_rows))
-    check(L.als_row_moments(ptr(row_ptr), ptr(col), ptr(val), nnz, n_rows, int(n_cols),
-                            ptr(other), ctypes.addressof(off), ptr(moments), ptr(total), ptr(w),
-                            w.numel(), stream_ptr(dev)), "als_row_moments")
-    return moments, total
-
-
-def bias_update(moments: torch.Tensor, damping: float, out: Optional[torch.Tensor] = None
-                ) -> torch.Tensor:
-    """sum_row / (damping + n_row) of a moments table (als_bias_update): f64 [n_rows], 0 for a
-    row without ratings."""
-    L = _lib.lib()
-    n_rows = int(moments.shape[0])
-    if out is None:
-        out = torch.empty(n_rows, dtype=torch.float64, device=moments.device)
-    d = _host_f64(damping)
-    check(L.als_bias_update(ptr(moments), n_rows, ctypes.addressof(d), ptr(out),
-                            stream_ptr(moments.device)), "als_bias_update")
-    return out
-
-
-def baseline_predict_rows(urow: torch.Tensor, irow: torch.Tensor, mu: float,
-                          bu: Optional[torch.Tensor], bi: Optional[torch.Tensor], n_users: int,
-                          n_items: int):
-    """mu + bu[urow] + bi[irow] for pairs of dense rows (int32; a row outside its table, -1
-    included, is an unknown id and adds nothing): (pred f32 [n], known uint8 [n], bit 0 = user
-    known, bit 1 = item known).  bu / bi: f64 device tables or None (all zero)."""
-    L = _lib.lib()
-    dev = urow.device
-    urow, irow = urow.to(torch.int32).contiguous(), irow.to(torch.int32).contiguous()
-    if urow.shape != irow.shape or urow.dim() != 1:
-        raise ValueError("baseline_predict_rows: urow and irow must be vectors of one length")
-    n = int(urow.numel())
-    pred = torch.empty(n, dtype=torch.float32, device=dev)
-    known = torch.empty(n, dtype=torch.uint8, device=dev)
-    m = _host_f64(mu)
-    check(L.als_baseline_predict(ptr(urow), ptr(irow), n, ctypes.addressof(m), ptr(bu),
-                                 int(n_users), ptr(bi), int(n_items), ptr(pred), ptr(known),
-                                 stream_ptr(dev)), "als_baseline_predict")
-    return pred, known
-
-
-def rating_stats_dict(moments: torch.Tensor) -> dict:
-    """count (int64), mean, std (population), std_sample (n - 1 in the denominator, NaN where
-    n <= 1), min and max of each row of a moments table; mean and the rest are NaN for a row
-    without ratings.  Device tensors."""
-    n, s, m2 = moments[:, 0], moments[:, 1], moments[:, 2]
-    nan = torch.full_like(n, float("nan"))
-    has = n > 0
-    return {"count": n.to(torch.int64), "mean": torch.where(has, s / n, nan),
-            "std": torch.where(has, torch.sqrt(m2 / n), nan),
-            "std_sample": torch.where(n > 1, torch.sqrt(m2 / (n - 1)), nan),
-            "min": moments[:, 3].clone(), "max": moments[:, 4].clone()}
-
-
-class Baseline:
-    """A fitted mean / bias predictor mu + b_u + b_i (ALSCore.fit_baseline): mu a float, bu /
-    bi f64 device tables in dense order (zeros where the method fits none), uidx / iidx the
-    id maps, history the training objective after every sweep."""
-
-    def __init__(self, method, mu, bu, bi, uidx: IdIndex, iidx: IdIndex, history, ws: Workspace,
-                 reg_user: float = 0.0, reg_item: float = 0.0):
-        self.method, self.mu, self.bu, self.bi = method, float(mu), bu, bi
-        self.uidx, self.iidx, self.history, self.ws = uidx, iidx, list(history), ws
-        self.reg_user, self.reg_item = float(reg_user), float(reg_item)
-        self.device = bu.device
-
-    def predict(self, users, items, return_known: bool = False):
-        """f32 prediction per pair; an id the fit did not see adds a zero bias, so a pair
-        unknown on both sides gets mu.  return_known: also the uint8 flags (bit 0 = user
-        known, bit 1 = item known)."""
-        u = _to_device(users, torch.int32, self.device)
-        i = _to_device(items, torch.int32, self.device)
-        pred, known = baseline_predict_rows(self.uidx.rows_of(u).to(torch.int32),
-                                            self.iidx.rows_of(i).to(torch.int32), self.mu,
-                                            self.bu, self.bi, self.uidx.n, self.iidx.n)
-        return (pred, known) if return_known else pred
-
-    def regression_metrics(self, users, items, ratings, through_origin: bool = False) -> dict:
-        """regression_dict's keys for the predictions against held-out ratings, every pair
-        used (dropped = 0): the moments are K8's column form over (ratings, predict())."""
-        r = _to_device(ratings, torch.float32, self.device)
-        pred = self.predict(users, items)
-        if r.numel() != pred.numel():
-            raise ValueError("users, items and ratings must have the same length")
-        m = regression_moments_cols(r.double(), pred.double(), self.ws)
-        return regression_dict(m.tolist(), through_origin)
-
-
-# ---------------------------------------------------------------------------
-# The engine
-# ---------------------------------------------------------------------------
 def make_engine(users, items, ratings, device=None):
     """The engine behind ALS.fit / ALS.train: one GPU (ALSCore), or — when this process
     is one rank of an initialised torch.distributed group of world size > 1 —
@@ -1448,11 +92,7 @@ class ALSCore:
         # computeYtY's task slots in a buffer of their own: written over the solve
         # workspace they would clobber its rating scale word, re-measured every half-sweep
         self.ws_yty = Workspace(self.device)
-        u = _to_device(users, torch.int32, self.device)
-        i = _to_device(items, torch.int32, self.device)
-        r = _to_device(ratings, torch.float32, self.device)
-        if not (u.numel() == i.numel() == r.numel()):
-            raise ValueError("users, items and ratings must have the same length")
+        u, i, r = self._triples(users, items, ratings)
         if u.numel() == 0:
             raise ValueError("ALS needs at least one rating")
         umin, umax = int(u.min()), int(u.max())
@@ -1468,6 +108,10 @@ class ALSCore:
         self.uidx.offset, self.iidx.offset = uoff, ioff
         self.user_block = build_block(u, self.uidx, i, self.iidx, r, self.ws, chunk)
         self.item_block = build_block(i, self.iidx, u, self.uidx, r, self.ws, chunk)
+        self._blank_state()
+
+    def _blank_state(self) -> None:
+        """What a core holds before its first fit, whichever way it was built."""
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._train_ex = {}  # user_side -> sorted training exclusion list (train_exclusion)
         self._fit_params = None  # reg / implicit / alpha / nonnegative of the last fit
@@ -1477,6 +121,8 @@ class ALSCore:
         self.U: Optional[torch.Tensor] = None
         self.V: Optional[torch.Tensor] = None
         self.rank = 0
+        # buffers of their own, made on first use: the solve workspace keeps its rating scale
+        self.ws_nnls = self.ws_obj = self.ws_rows = None
 
     @classmethod
     def from_factors(cls, user_ids, U, item_ids, V, device=None) -> "ALSCore":
@@ -1491,12 +137,7 @@ class ALSCore:
         self.nnz = 0
         self._auto_chunk = False
         self.user_block = self.item_block = None
-        self._train_ex = {}
-        self._fit_params = None
-        self._touched = None
-        self.objective_history = []
-        self.iterations_run = 0
-        self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._blank_state()
         U = _to_device(U, torch.float32, self.device)
         V = _to_device(V, torch.float32, self.device)
         rank = int(U.shape[1])
@@ -1530,6 +171,53 @@ class ALSCore:
     @property
     def n_items(self) -> int:
         return self.iidx.n
+
+    # ---- checks and conversions the public methods share ----
+    def _need_ratings(self, who: str) -> None:
+        if self.user_block is None:
+            raise ValueError(f"{who} needs the ratings the model was fitted on; this core "
+                             "was built from saved factors (from_factors / load) and has none")
+
+    def _need_factors(self, who: str) -> None:
+        if self.U is None or self.V is None:
+            raise ValueError(f"{who} needs factors: fit() the core or build it from_factors")
+
+    def _pairs(self, users, items):
+        """users, items as int32 device vectors of one length."""
+        u = _to_device(users, torch.int32, self.device)
+        i = _to_device(items, torch.int32, self.device)
+        if u.numel() != i.numel():
+            raise ValueError("users and items must have the same length")
+        return u, i
+
+    def _triples(self, users, items, ratings):
+        """users, items (int32) and ratings (f32) as device vectors of one length."""
+        u = _to_device(users, torch.int32, self.device)
+        i = _to_device(items, torch.int32, self.device)
+        r = _to_device(ratings, torch.float32, self.device)
+        if not (u.numel() == i.numel() == r.numel()):
+            raise ValueError("users, items and ratings must have the same length")
+        return u, i, r
+
+    def _known_rows(self, idx: IdIndex, ids):
+        """(keys int32, dense rows int64) of the distinct ids `idx` knows, ascending."""
+        keys = torch.unique(_to_device(ids, torch.int32, self.device))
+        rows = idx.rows_of(keys)
+        known = rows >= 0
+        return keys[known], rows[known]
+
+    def _allow_bits(self, idx: IdIndex, candidates):
+        """The allow mask of the rows of `idx` named by `candidates` (ids; unknown ones
+        dropped), None for no restriction."""
+        if candidates is None:
+            return None
+        c = _to_device(candidates, torch.int32, self.device)
+        return _filters.pack_allow_bits(idx.rows_of(c), idx.n)
+
+    def _empty_lists(self, m: int, t: int):
+        """The (ids int32, scores f32) pair of m lists with t slots, unfilled."""
+        return (torch.empty((m, t), dtype=torch.int32, device=self.device),
+                torch.empty((m, t), dtype=torch.float32, device=self.device))
 
     # Spark ALS.initialize: unit-norm Gaussian rows, fp32.
     def init_factors(self, rank: int, seed: int = 0, U0=None) -> None:
@@ -1568,7 +256,7 @@ class ALSCore:
     def _half_sweep_nnls(self, block, Y, n_src, X, reg, implicit, alpha):
         """One computeFactors pass with Spark's NNLSSolver (K13); a buffer of its own, so the
         solve workspace keeps its rating scale."""
-        if getattr(self, "ws_nnls", None) is None:
+        if self.ws_nnls is None:
             self.ws_nnls = Workspace(self.device)
         yty = compute_yty(Y, n_src, self.rank, self.ws_yty) if implicit else None
         nnls_rows(block.row_ptr, block.col, block.val, Y, n_src, self.rank, reg, implicit, alpha,
@@ -1615,16 +303,13 @@ class ALSCore:
         (times reg already), "scale" (the sum of the absolute values of everything added:
         the size rounding errors are relative to), "n", "n_positive"}.  Deterministic: two
         calls on the same factors return the same bits.  One host sync."""
-        if self.user_block is None:
-            raise ValueError("objective needs the ratings the model was fitted on; this core "
-                             "was built from saved factors (from_factors / load) and has none")
+        self._need_ratings("objective")
         if self.U is None or self.V is None:
             raise ValueError("objective needs factors: fit() the core or init_factors() first")
         if reg < 0 or alpha < 0:
             raise ValueError(f"reg and alpha must be >= 0, got {reg}, {alpha}")
-        if getattr(self, "ws_obj", None) is None:
-            # a buffer of its own: the solve workspace keeps the rating scale between
-            # half-sweeps, and observing a fit must not make it re-measure anything
+        if self.ws_obj is None:
+            # observing a fit must not make the solve workspace re-measure its rating scale
             self.ws_obj = Workspace(self.device)
         n = len(OBJECTIVE_SIDE)
         out = torch.zeros(2 * n + 1, dtype=torch.float64, device=self.device)
@@ -1716,13 +401,12 @@ class ALSCore:
         row_ptr, col, val = gather_rows(*csr, rows)
         yty = compute_yty(*(yty_of or (Y, n_src)), self.rank, self.ws_yty) if p["implicit"] else None
         if p["nonnegative"]:
-            if getattr(self, "ws_nnls", None) is None:
+            if self.ws_nnls is None:
                 self.ws_nnls = Workspace(self.device)
             X, n_used, _ = nnls_rows(row_ptr, col, val, Y, n_src, self.rank, p["reg"],
                                      p["implicit"], p["alpha"], yty, self.ws_nnls)
             return X, n_used
-        if getattr(self, "ws_rows", None) is None:
-            # a buffer of its own: the solve workspace keeps its rating scale word
+        if self.ws_rows is None:
             self.ws_rows = Workspace(self.device)
         status = torch.zeros(1, dtype=torch.int32, device=self.device)
         X, n_used = fold_in_rows(row_ptr, col, val, Y, n_src, self.rank, p["reg"], p["implicit"],
@@ -1775,14 +459,8 @@ class ALSCore:
         "touched_items" (int64 dense rows in the grown maps, ascending: the rows whose
         rating lists changed)}; the touched rows of every add since the last fit are kept
         for refresh()."""
-        if self.user_block is None:
-            raise ValueError("add_ratings needs the ratings the model was fitted on; this core "
-                             "was built from saved factors (from_factors / load) and has none")
-        u = _to_device(users, torch.int32, self.device)
-        i = _to_device(items, torch.int32, self.device)
-        r = _to_device(ratings, torch.float32, self.device)
-        if not (u.numel() == i.numel() == r.numel()):
-            raise ValueError("users, items and ratings must have the same length")
+        self._need_ratings("add_ratings")
+        u, i, r = self._triples(users, items, ratings)
         empty = torch.empty(0, dtype=torch.int64, device=self.device)
         if u.numel() == 0:
             return {"added": 0, "new_users": empty.to(torch.int32), "new_items":
@@ -1830,17 +508,25 @@ class ALSCore:
             self.U, self.V = U, V
         self._train_ex = {}
         self.ws.rating_scale_key = None   # the batch may hold the largest |rating|
-        if self._touched is not None:    # rows touched earlier, in the grown numbering
-            tu, ti = self._touched
-            tu = tu if umap is None else umap[tu].long()
-            ti = ti if imap is None else imap[ti].long()
-            touched_all = (torch.unique(torch.cat([tu, touched_u])),
-                           torch.unique(torch.cat([ti, touched_i])))
-        else:
-            touched_all = (touched_u, touched_i)
-        self._touched = touched_all
+        self._retouch((umap, imap), (touched_u, touched_i))
         return {"added": st["added"], "new_users": uidx.ids()[new_u], "new_items":
                 iidx.ids()[new_i], "touched_users": touched_u, "touched_items": touched_i}
+
+    def _retouch(self, maps, new_touched) -> None:
+        """The rows refresh() owes a re-solve after the id maps moved: the (user, item) rows
+        touched earlier, renumbered through `maps` (int32 old row -> new row, -1 = the row
+        left and is dropped, None = this side's numbering is unchanged), united with
+        `new_touched` (ascending int64 rows in the new numbering)."""
+        if self._touched is None:
+            self._touched = tuple(new_touched)
+            return
+        touched = []
+        for mp, earlier, new in zip(maps, self._touched, new_touched):
+            if mp is not None:
+                earlier = mp[earlier].long()
+                earlier = earlier[earlier >= 0]
+            touched.append(torch.unique(torch.cat([earlier, new])))
+        self._touched = tuple(touched)
 
     def _grown_factors(self, n_u, n_i, umap, imap, new_u, new_i, user_csr, item_csr, seed):
         """add_ratings step d: (U, V) for the grown id maps."""
@@ -1895,9 +581,7 @@ class ALSCore:
         user's 12 ratings (1 + 12 rows) take 1.0 ms, 0.6 of a full iteration, but a batch of
         10^4 ratings (19 thousand rows) 12.6 ms, 7.5 iterations — there refit(1) is the
         cheaper call.  Returns self."""
-        if self.user_block is None:
-            raise ValueError("refresh needs the ratings the model was fitted on; this core "
-                             "was built from saved factors (from_factors / load) and has none")
+        self._need_ratings("refresh")
         if self.U is None or self.V is None:
             raise ValueError("refresh needs factors: fit() the core first")
         p = self._update_params(reg, implicit, alpha, nonnegative)
@@ -1922,9 +606,7 @@ class ALSCore:
         the last fit (fit_kwargs override them and pass objective_every / tol through).
         Spark's order solves the items first from U alone and never reads V, so continuing
         from the current U is continuing the fit."""
-        if self.user_block is None:
-            raise ValueError("refit needs the ratings the model was fitted on; this core "
-                             "was built from saved factors (from_factors / load) and has none")
+        self._need_ratings("refit")
         if self.U is None or self.rank < 1:
             raise ValueError("refit needs factors: fit() the core first")
         if "U0" in fit_kwargs or "rank" in fit_kwargs:
@@ -1938,13 +620,8 @@ class ALSCore:
     def _listed_pairs(self, users, items, who: str):
         """The distinct (user, item) pairs of a batch: (u int32, i int32, ur, ir int64 dense
         rows, -1 = unknown)."""
-        if self.user_block is None:
-            raise ValueError(f"{who} needs the ratings the model was fitted on; this core "
-                             "was built from saved factors (from_factors / load) and has none")
-        u = _to_device(users, torch.int32, self.device)
-        i = _to_device(items, torch.int32, self.device)
-        if u.numel() != i.numel():
-            raise ValueError("users and items must have the same length")
+        self._need_ratings(who)
+        u, i = self._pairs(users, items)
         if u.numel():
             key = torch.unique((u.long() << 32) | (i.long() & 0xFFFFFFFF))
             low = key & 0xFFFFFFFF
@@ -1952,10 +629,10 @@ class ALSCore:
             i = torch.where(low >= (1 << 31), low - (1 << 32), low).to(torch.int32)
         return u, i, self.uidx.rows_of(u), self.iidx.rows_of(i)
 
-    def _mark_removed(self, ur, ir):
+    def _mark_removed(self, ur, ir, who: str):
         """Both sides' K18 mark pass for the distinct stored-id pairs (ur, ir) (int64 dense
         rows).  Returns (user marks, item marks, stored copies dropped per pair in (ur, ir)
-        order of the user side's sort)."""
+        order of the user side's sort, the ratings that stay)."""
         n_u, n_i = self.n_users, self.n_items
         ub, ib = self.user_block, self.item_block
         ku = torch.sort(ur * n_i + ir).values            # by user row, then item row
@@ -1964,7 +641,10 @@ class ALSCore:
         del_i = _delete_csr(ki // n_u, ki % n_u, n_i)
         mu = remove_mark(ub.row_ptr, ub.col, *del_u, self.ws, count_hits=True)
         mi = remove_mark(ib.row_ptr, ib.col, *del_i, self.ws)
-        return mu, mi, mu[3]
+        nnz = int(mu[1][-1])
+        if nnz != int(mi[1][-1]):
+            raise RuntimeError(f"{who}: the two sides disagree on what stays")
+        return mu, mi, mu[3], nnz
 
     def remove_ratings(self, users, items) -> dict:
         """Take ratings back from the core in place: every stored copy of every listed (user,
@@ -2006,10 +686,7 @@ class ALSCore:
         known = (ur >= 0) & (ir >= 0)
         if not bool(known.any()):
             return info
-        mu, mi, hits = self._mark_removed(ur[known], ir[known])
-        nnz = int(mu[1][-1])
-        if nnz != int(mi[1][-1]):
-            raise RuntimeError("remove_ratings: the two sides disagree on what stays")
+        mu, mi, hits, nnz = self._mark_removed(ur[known], ir[known], "remove_ratings")
         if nnz == self.nnz:
             return info
         if nnz == 0:
@@ -2046,13 +723,7 @@ class ALSCore:
             self.U, self.V = U, V
         self._train_ex = {}
         self.ws.rating_scale_key = None   # the largest |rating| may have left
-        touched = []
-        for s, earlier in zip(side, self._touched or (empty, empty)):
-            if s["map"] is not None:      # rows touched earlier, in the new numbering
-                earlier = s["map"][earlier].long()
-                earlier = earlier[earlier >= 0]
-            touched.append(torch.unique(torch.cat([earlier, s["touched"]])))
-        self._touched = tuple(touched)
+        self._retouch((su["map"], si["map"]), (su["touched"], si["touched"]))
         info.update(removed=removed,
                     missing=int(u.numel()) - int(known.sum()) + int((hits == 0).sum()),
                     left_users=su["left"], left_items=si["left"], touched_users=su["touched"],
@@ -2060,9 +731,7 @@ class ALSCore:
         return info
 
     def _remove_rows(self, ids, user_side: bool, who: str) -> dict:
-        if self.user_block is None:
-            raise ValueError(f"{who} needs the ratings the model was fitted on; this core "
-                             "was built from saved factors (from_factors / load) and has none")
+        self._need_ratings(who)
         ids = torch.unique(_to_device(ids, torch.int32, self.device))
         idx, block, other = ((self.uidx, self.user_block, self.iidx) if user_side else
                              (self.iidx, self.item_block, self.uidx))
@@ -2098,14 +767,8 @@ class ALSCore:
         state and the added state are computed first and stored at the end: nothing is
         changed when the call raises.  Returns add_ratings' report for the de-duplicated
         batch plus "replaced", the stored ratings that went."""
-        if self.user_block is None:
-            raise ValueError("set_ratings needs the ratings the model was fitted on; this core "
-                             "was built from saved factors (from_factors / load) and has none")
-        u = _to_device(users, torch.int32, self.device)
-        i = _to_device(items, torch.int32, self.device)
-        r = _to_device(ratings, torch.float32, self.device)
-        if not (u.numel() == i.numel() == r.numel()):
-            raise ValueError("users, items and ratings must have the same length")
+        self._need_ratings("set_ratings")
+        u, i, r = self._triples(users, items, ratings)
         if u.numel() == 0:
             return dict(self.add_ratings(u, i, r), replaced=0)
         key = (u.long() << 32) | (i.long() & 0xFFFFFFFF)
@@ -2119,10 +782,7 @@ class ALSCore:
         ucsr = icsr = None
         nnz = self.nnz
         if bool(known.any()):
-            mu, mi, _ = self._mark_removed(ur[known], ir[known])
-            nnz = int(mu[1][-1])
-            if nnz != int(mi[1][-1]):
-                raise RuntimeError("set_ratings: the two sides disagree on what stays")
+            mu, mi, _, nnz = self._mark_removed(ur[known], ir[known], "set_ratings")
             if nnz != self.nnz:   # rows stay where they are, empty or not: no map, no shrink
                 ub, ib = self.user_block, self.item_block
                 ucsr = (mu[2],) + remove_compact(ub.col, ub.val, mu[0], mu[1], None, ib.n_rows, nnz)
@@ -2180,28 +840,22 @@ class ALSCore:
             raise ValueError("exclude='train' needs the ratings the model was fitted on; this "
                              "core was built from saved factors (from_factors / load) and has "
                              "none: pass the pairs to exclude explicitly")
-        L = _lib.lib()
         mine, opp = (self.user_block, self.item_block) if user_side else (self.item_block,
                                                                           self.user_block)
-        dev = self.device
-        i32 = dict(dtype=torch.int32, device=dev)
+        i32 = dict(dtype=torch.int32, device=self.device)
         deg = opp.row_ptr[1:] - opp.row_ptr[:-1]
         # COO of the opposite block: its row (= the other side's dense row) per entry,
-        # ascending; its col = this side's dense row
+        # ascending; its col = this side's dense row.  Both are dense rows already, so the
+        # two id maps K1 looks them up in are the identity
         other = torch.repeat_interleave(torch.arange(opp.n_rows, **i32), deg)
-        row_map = torch.arange(mine.n_rows, **i32)
-        col_map = torch.arange(opp.n_rows, **i32)
-        row_ptr = torch.empty(mine.n_rows + 1, dtype=torch.int64, device=dev)
-        col = torch.empty(max(opp.nnz, 1), **i32)
-        val = torch.empty(max(opp.nnz, 1), dtype=torch.float32, device=dev)  # (unused copy)
-        w = self.ws.get(L.als_csr_workspace_bytes(opp.nnz, mine.n_rows))
-        check(L.als_csr_build(ptr(opp.col), ptr(row_map), ptr(other), ptr(col_map), ptr(opp.val),
-                              opp.nnz, mine.n_rows, ptr(row_ptr), ptr(col), ptr(val), ptr(w),
-                              w.numel(), stream_ptr(dev)), "als_csr_build (exclusion list)")
+        rows = torch.arange(mine.n_rows, **i32)
+        cols = torch.arange(opp.n_rows, **i32)
         # K1 has no way to skip the values: the fp32 copy and the COO index go as soon as
         # the sort has run (peak: 3 x 4 B per rating beside the two rating blocks and
         # K1's workspace; kept: 4 B per rating per side)
-        del val, other
+        row_ptr, col = build_csr(opp.col, IdIndex(rows, rows, mine.n_rows), other,
+                                 IdIndex(cols, cols, opp.n_rows), opp.val, self.ws)[:2]
+        del other
         self._train_ex[bool(user_side)] = (row_ptr, col)
         return row_ptr, col
 
@@ -2211,7 +865,7 @@ class ALSCore:
         (query ids, other ids) pairs (host or device; unknown ids dropped, as predict's
         inner join does); candidates: None or ids of the other side (unknown dropped)."""
         qi, _, oi, _ = self._sides(user_side)
-        beg = end = col = bits = None
+        beg = end = col = None
         if isinstance(exclude, str):
             if exclude != "train":
                 raise ValueError(f"exclude must be None, 'train' or (ids, ids) pairs, got {exclude!r}")
@@ -2226,10 +880,7 @@ class ALSCore:
             if rows is not None:
                 beg, end = beg[rows], end[rows]
             beg, end = beg.contiguous(), end.contiguous()
-        if candidates is not None:
-            c = _to_device(candidates, torch.int32, self.device)
-            bits = _filters.pack_allow_bits(oi.rows_of(c), oi.n)
-        return beg, end, col, bits
+        return beg, end, col, self._allow_bits(oi, candidates)
 
     def _topk(self, Q, n_q, user_side, top, exclude, candidates, rows=None):
         _, _, oi, Vo = self._sides(user_side)
@@ -2256,15 +907,10 @@ class ALSCore:
         (ascending) -> (keys, ids [m, t], scores [m, t]).  exclude / candidates as
         recommend_all (the subset's rows point into the one exclusion list)."""
         qi, Q, oi, Vo = self._sides(user_side)
-        q = _to_device(ids, torch.int32, self.device)
-        keys = torch.unique(q)
-        rows = qi.rows_of(keys)
-        known = rows >= 0
-        keys, rows = keys[known], rows[known]
+        keys, rows = self._known_rows(qi, ids)
         t = min(int(top), oi.n)
         if keys.numel() == 0:
-            return keys, torch.empty((0, t), dtype=torch.int32, device=self.device), \
-                torch.empty((0, t), dtype=torch.float32, device=self.device)
+            return (keys, *self._empty_lists(0, t))
         Qs = Q.index_select(0, rows.long()).contiguous()
         idx, sc = self._topk(Qs, keys.numel(), user_side, top, exclude, candidates, rows.long())
         return keys, ids_of(oi.ids(), idx[:, :t]), sc[:, :t]
@@ -2272,17 +918,12 @@ class ALSCore:
     # ---- K12: which rows are like this one? ----
     def _similar_args(self, top, user_side: bool, candidates):
         """(index, table, t, kernel top, allow mask) of a neighbour search on one side."""
-        if self.U is None or self.V is None:
-            raise ValueError("similar needs factors: fit() the core or build it from_factors")
+        self._need_factors("similar")
         top = int(top)
         if not 1 <= top <= SIMILAR_MAX_TOP:
             raise ValueError(f"top must be in [1, {SIMILAR_MAX_TOP}], got {top}")
         qi, T, _, _ = self._sides(user_side)
-        bits = None
-        if candidates is not None:
-            c = _to_device(candidates, torch.int32, self.device)
-            bits = _filters.pack_allow_bits(qi.rows_of(c), qi.n)
-        return qi, T, min(top, qi.n - 1), bits
+        return qi, T, min(top, qi.n - 1), self._allow_bits(qi, candidates)
 
     def similar(self, ids, top: int, user_side: bool = False, *, candidates=None):
         """Cosine nearest neighbours inside one side's factors: for the distinct known ids
@@ -2298,15 +939,10 @@ class ALSCore:
         more take the unit copy + K5 route (similar_rows_unit).  Both keep this contract,
         scores within 1e-5 of each other; neighbours closer than that may swap places."""
         qi, T, t, bits = self._similar_args(top, user_side, candidates)
-        q = _to_device(ids, torch.int32, self.device)
-        keys = torch.unique(q)
-        rows = qi.rows_of(keys)
-        known = rows >= 0
-        keys, rows = keys[known], rows[known]
+        keys, rows = self._known_rows(qi, ids)
         m = int(keys.numel())
         if m == 0 or t == 0:
-            return keys, torch.empty((m, t), dtype=torch.int32, device=self.device), \
-                torch.empty((m, t), dtype=torch.float32, device=self.device)
+            return (keys, *self._empty_lists(m, t))
         if m >= SIMILAR_SWEEP_MIN_ROWS:
             idx, sc = similar_rows_unit(rows, T, qi.n, self.rank, t, bits)
         else:
@@ -2321,8 +957,7 @@ class ALSCore:
         sides (never n / 16 passes of K12)."""
         qi, T, t, bits = self._similar_args(top, user_side, candidates)
         if t == 0:
-            return qi.ids(), torch.empty((qi.n, 0), dtype=torch.int32, device=self.device), \
-                torch.empty((qi.n, 0), dtype=torch.float32, device=self.device)
+            return (qi.ids(), *self._empty_lists(qi.n, 0))
         idx, sc = similar_rows_unit(None, T, qi.n, self.rank, t, bits)
         return qi.ids(), ids_of(qi.ids(), idx), sc
 
@@ -2343,9 +978,7 @@ class ALSCore:
         pairwise cosine, NaN under two picks).
         The query rows go through in chunks of chunk_rows (None: as many as keep the pool
         arrays within DIVERSIFY_POOL_BYTES); the result does not depend on the chunking."""
-        if self.U is None or self.V is None:
-            raise ValueError("recommend_diverse needs factors: fit() the core or build it "
-                             "from_factors")
+        self._need_factors("recommend_diverse")
         top, lam = int(top), float(trade_off)
         if top < 1:
             raise ValueError(f"top must be >= 1, got {top}")
@@ -2398,9 +1031,7 @@ class ALSCore:
         ids of the OTHER side — items for user_side=True, as recommend_all's ids — and the
         result is f64 [n] on the device, each list's mean pairwise cosine between the factor
         rows of its known ids (an unknown id is an open slot; NaN under two known ids)."""
-        if self.U is None or self.V is None:
-            raise ValueError("list_similarity needs factors: fit() the core or build it "
-                             "from_factors")
+        self._need_factors("list_similarity")
         _, _, oi, Vo = self._sides(user_side)
         lists = _to_device(id_lists, torch.int32, self.device)
         if lists.dim() != 2:
@@ -2455,9 +1086,7 @@ class ALSCore:
             if exclude is not None:
                 raise ValueError("exclude= shapes the lists made with top=; lists given as "
                                  "id_lists are taken as they are")
-        if self.U is None or self.V is None:
-            raise ValueError("list_metrics needs factors: fit() the core or build it "
-                             "from_factors")
+        self._need_factors("list_metrics")
         qi, Q, oi, _ = self._sides(user_side)
         keys = None
         if id_lists is not None:
@@ -2507,8 +1136,7 @@ class ALSCore:
     def _fold_in(self, ids, other_ids, ratings, reg, implicit, alpha, user_side,
                  nonnegative=False):
         """(keys, X [m, ld], n_used, row_ptr, col) of fold_in, X with its padding columns."""
-        if self.U is None or self.V is None:
-            raise ValueError("fold_in needs factors: fit() the core or build it from_factors")
+        self._need_factors("fold_in")
         if reg < 0 or alpha < 0:
             raise ValueError(f"reg and alpha must be >= 0, got {reg}, {alpha}")
         _, _, oi, Y = self._sides(user_side)
@@ -2569,18 +1197,15 @@ class ALSCore:
         keys, Q = keys[keep], X[keep].contiguous()
         m = int(keys.numel())
         if m == 0:
-            return keys, torch.empty((0, t), dtype=torch.int32, device=self.device), \
-                torch.empty((0, t), dtype=torch.float32, device=self.device)
-        beg = end = ex = bits = None
+            return (keys, *self._empty_lists(0, t))
+        beg = end = ex = None
         if exclude_rated:
             n_all = int(row_ptr.numel()) - 1
             new_row = torch.repeat_interleave(torch.arange(n_all, device=self.device),
                                               row_ptr[1:] - row_ptr[:-1])
             beg, end, ex = _filters.exclusion_lists(new_row, col, n_all)
             beg, end = beg[keep].contiguous(), end[keep].contiguous()
-        if candidates is not None:
-            c = _to_device(candidates, torch.int32, self.device)
-            bits = _filters.pack_allow_bits(oi.rows_of(c), oi.n)
+        bits = self._allow_bits(oi, candidates)
         if beg is None and bits is None:
             idx, sc = topk_rows(Q, m, Vo, oi.n, self.rank, top)
         else:
@@ -2612,13 +1237,7 @@ class ALSCore:
         uniq, inv = torch.unique(dense[dense >= 0], return_inverse=True)
         pair_row = torch.full_like(dense, -1)
         pair_row[dense >= 0] = inv
-        beg = block.row_ptr[uniq]
-        lens = block.row_ptr[uniq + 1] - beg
-        row_ptr = torch.zeros(uniq.numel() + 1, dtype=torch.int64, device=self.device)
-        row_ptr[1:] = torch.cumsum(lens, 0)
-        src = (torch.repeat_interleave(beg - row_ptr[:-1], lens)
-               + torch.arange(int(row_ptr[-1]), device=self.device))
-        return pair_row, row_ptr, block.col[src].contiguous(), block.val[src].contiguous()
+        return (pair_row, *gather_rows(block.row_ptr, block.col, block.val, uniq))
 
     def explain(self, users, items, top_n: int = 10, *, reg, implicit=False, alpha=1.0,
                 user_side: bool = True, ratings=None):
@@ -2644,16 +1263,12 @@ class ALSCore:
         top_n = int(top_n)
         if not 1 <= top_n <= EXPLAIN_MAX_TOP:
             raise ValueError(f"top_n must be in [1, {EXPLAIN_MAX_TOP}], got {top_n}")
-        if self.U is None or self.V is None:
-            raise ValueError("explain needs factors: fit() the core or build it from_factors")
+        self._need_factors("explain")
         reg, alpha = float(reg), float(alpha)
         if reg < 0 or alpha < 0:
             raise ValueError(f"reg and alpha must be >= 0, got {reg}, {alpha}")
         _, _, oi, Y = self._sides(user_side)
-        u = _to_device(users, torch.int32, self.device).reshape(-1)
-        i = _to_device(items, torch.int32, self.device).reshape(-1)
-        if u.numel() != i.numel():
-            raise ValueError("users and items must have the same length")
+        u, i = (x.reshape(-1) for x in self._pairs(users, items))
         q, o = (u, i) if user_side else (i, u)
         pair_row, row_ptr, col, val = self._explain_rows_of(q, bool(user_side), ratings)
         keep = pair_row >= 0
@@ -2705,10 +1320,7 @@ class ALSCore:
         at = int(at)
         if at < 1 or at > MAX_RANK_AT:
             raise ValueError(f"at must be in [1, {MAX_RANK_AT}], got {at}")
-        u = _to_device(users, torch.int32, self.device)
-        i = _to_device(items, torch.int32, self.device)
-        if u.numel() != i.numel():
-            raise ValueError("users and items must have the same length")
+        u, i = self._pairs(users, items)
         q, o = (qi.rows_of(u), oi.rows_of(i)) if user_side else (qi.rows_of(i), oi.rows_of(u))
         keep = (q >= 0) & (o >= 0)
         if threshold is not None:
@@ -2759,14 +1371,9 @@ class ALSCore:
         positions: also "row" / "col" (query-row index into "keys" order and dense row of
         the other side, per relevant pair), "above", "tied" (int32 per pair, -1 for an
         inadmissible one) and "n_adm" (int32 per query row), on the device."""
-        if self.U is None or self.V is None:
-            raise ValueError("full_rank_metrics needs factors: fit() the core or build it "
-                             "from_factors")
+        self._need_factors("full_rank_metrics")
         qi, Q, oi, Vo = self._sides(user_side)
-        u = _to_device(users, torch.int32, self.device)
-        i = _to_device(items, torch.int32, self.device)
-        if u.numel() != i.numel():
-            raise ValueError("users and items must have the same length")
+        u, i = self._pairs(users, items)
         r = None
         if threshold is not None or weighted:
             if ratings is None:
@@ -2821,14 +1428,8 @@ class ALSCore:
         one fused pass (K8, als_regression_moments): no prediction column is materialised.
         Pairs with an unknown id are left out and counted (rmse's inner join).  Returns
         regression_dict's keys: mse, rmse, mae, r2, var, n, dropped, meanLabel, varLabel."""
-        if self.U is None or self.V is None:
-            raise ValueError("regression_metrics needs factors: fit() the core or build it "
-                             "from_factors")
-        u = _to_device(users, torch.int32, self.device)
-        i = _to_device(items, torch.int32, self.device)
-        r = _to_device(ratings, torch.float32, self.device)
-        if not (u.numel() == i.numel() == r.numel()):
-            raise ValueError("users, items and ratings must have the same length")
+        self._need_factors("regression_metrics")
+        u, i, r = self._triples(users, items, ratings)
         m = regression_moments_pairs(u, i, r, self.uidx, self.iidx, self.U, self.V, self.rank,
                                      self.ws)
         return regression_dict(m.tolist(), through_origin)

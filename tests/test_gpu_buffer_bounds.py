@@ -137,7 +137,7 @@ class Mem:
 
 def _call(name, *args):
     """One ctypes call of the library: tensors as device pointers, None as NULL, the current
-    stream appended (the marshalling of engine.py)."""
+    stream appended (the marshalling of the kernels/*.py bindings)."""
     conv = [(0 if a is None else a.data_ptr()) if (a is None or isinstance(a, torch.Tensor))
             else a for a in args]
     _lib.check(getattr(_lib.lib(), name)(*conv, _lib.stream_ptr(DEV)), name)

@@ -6,7 +6,8 @@ the second trip.  The sizes come from the caps in the sources (tests/grid_caps.p
 itself (no loop), + 1 (one wave makes a second trip), + 5 (a last group of one row whose other
 waves skip the trip) and twice the cap + 1 (three trips).
 
-Each test runs the entry point through the engine.py wrapper of the kernel's own test file,
+Each test runs the entry point through the kernels/*.py wrapper (reached as engine.NAME) of
+the kernel's own test file,
 compares the per-row outputs on ALL rows (those at and past the cap are the point) and the sums
 with a vectorised reference (held to the older row-by-row references on a prefix in
 test_grid_caps_cpu.py), and calls twice for identical bytes.  The bars are those of the
