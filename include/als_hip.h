@@ -906,6 +906,62 @@ int als_csr_remove_compact(const int32_t* col_old, const float* val_old, int64_t
                            const int32_t* new_of_old_col, int32_t n_cols_old, int32_t* col_out,
                            float* val_out, int64_t nnz_out, void* stream);
 
+/* ---- K19: co-rated neighbours ("who rated X also rated Y": the item-based collaborative
+ *      filtering neighbourhood of Sarwar et al. 2001, from the ratings and not the factors;
+ *      the reference and Spark have no counterpart) ----------------------------------------- */
+
+/* Added under ABI 9 without a version bump: four new symbols only, nothing existing changes.
+ * For each of n_q query rows of one CSR side, the `top` other rows of the SAME side that share
+ * the most raters with it: one row of the sparse product B^T B per query, never formed.
+ *   queried side  row_ptr_q int64 [n + 1], col_q int32 (dense rows of the other side)
+ *   other side    row_ptr_o int64 [n_o + 1], col_o int32 (dense rows of the queried side):
+ *                 the two CSR sides K1 builds of one rating set; the values are never read
+ *   q_rows        int32 [n_q] dense rows of the queried side; a row outside [0, n) and a row
+ *                 without entries get an all-open list; a row given twice gets two lists
+ * With n_a the entries of row a, the common count of a pair is
+ *   c(a, b) = sum over rows u of the other side of (entries of a by u) x (entries of b by u),
+ * duplicate entries counting with their multiplicity (without duplicates: the number of u that
+ * rated both).  measure: 0 "count" (float)c; 1 "jaccard" (float)((double)c / (double)(n_a + n_b
+ * - c)); 2 "cosine" (float)((double)c / sqrt((double)n_a * (double)n_b)) (set cosine): one fp64
+ * expression of three integers, rounded once to fp32.  Row b is listed for query a when
+ * b != a (by dense row), c(a, b) >= min_common (>= 1) and bit b of allow_bits is set
+ * (als_topk_filtered's mask; NULL: every row).  Order: score descending, then row ascending
+ * (the exact 64-bit key of als_topk).  Outputs idx int32, score f32 and common int32 (the
+ * count c of each listed row), each [n_q, top]; open slots hold idx -1, score -inf, common 0.
+ * Every sum is an integer add (c < 2^31 is the caller's to ensure), so the results are exact
+ * and the same bits whatever the launch geometry, `pass`, `task`, or the order workgroups
+ * finish in.
+ * Queries go through in passes of `pass` (0 = 32; at most 64), each query in flight owning a
+ * strip of n int32 counters in the scratch.  A query row is cut into tasks of `task` entries
+ * (0 = als_co_rated_task(); at most 2^20), dealt over a fixed grid, so the most-rated row is
+ * spread over the device; for each entry u of its task a wavefront walks u's row of the other
+ * side and adds 1 per entry to the strip, through K15's direct-mapped LDS cache
+ * (als_co_rated_window() slots: an LDS add on a hit, one global add on a miss).  One wavefront
+ * per (slice of at least 512 rows, query) then ranks its counters, keeps its `top` best and
+ * stores zeros over the counters it has read; a merge launch (two stages past 64 slices)
+ * orders the lists.  Non-zero pass / task exist so that tests reach many passes and many
+ * tasks at small shapes.
+ * Scratch: als_co_rated_scratch_bytes(n, n_q, top, pass) bytes (sized for min(n_q, pass)
+ * queries in flight), 16-byte aligned, and it need not be initialised: the call zeroes the
+ * strips on entry and every pass leaves them zero, so the strips are zero after the call and
+ * no result depends on what the scratch or the outputs held before.  The strips are the first
+ * 4 min(n_q, pass) n bytes of the scratch.
+ * Checked on the host before any launch: top outside [1, 256], measure outside [0, 3),
+ * min_common < 1, pass outside [0, 64], task outside [0, 2^20], a negative size, n or
+ * n_o >= 2^31 - 1 and (when n_q > 0) a null q_rows, row pointer, output or misaligned scratch
+ * are ALS_EINVAL; a short scratch is ALS_EWORKSPACE; n_q == 0 is a no-op.
+ * als_co_rated_scratch_bytes returns 0 for sizes als_co_rated rejects.
+ * Cost per query and beside the other routes: DESIGN.md section K19. */
+int32_t als_co_rated_task(void);
+int32_t als_co_rated_window(void);
+size_t als_co_rated_scratch_bytes(int64_t n, int32_t n_q, int32_t top, int32_t pass);
+int als_co_rated(const int64_t* row_ptr_q, const int32_t* col_q, int64_t n,
+                 const int64_t* row_ptr_o, const int32_t* col_o, int64_t n_o,
+                 const int32_t* q_rows, int32_t n_q, int32_t measure, int32_t min_common,
+                 const uint32_t* allow_bits, int32_t top, int32_t pass, int32_t task,
+                 int32_t* idx, float* score, int32_t* common,
+                 void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -120,6 +120,11 @@ SIGNATURES = {
     "als_csr_remove_scratch_bytes": (SZ, [I64, I32]),
     "als_csr_remove_mark": (ctypes.c_int, [P, P, I64, I32, P, P, I64, P, P, P, P, P, SZ, P]),
     "als_csr_remove_compact": (ctypes.c_int, [P, P, I64, P, P, P, I32, P, P, I64, P]),
+    "als_co_rated_task": (I32, []),
+    "als_co_rated_window": (I32, []),
+    "als_co_rated_scratch_bytes": (SZ, [I64, I32, I32, I32]),
+    "als_co_rated": (ctypes.c_int, [P, P, I64, P, P, I64, P, I32, I32, I32, P, I32, I32, I32, P, P,
+                                    P, P, SZ, P]),
 }
 
 ABI_VERSION = 9

@@ -20,6 +20,7 @@
 //
 // als_list_concentration and als_list_novelty sum in fp64 in a fixed order (partial_sums.h).
 #include "als_common.h"
+#include "lx_cache.h"
 #include "partial_sums.h"
 #include <math.h>
 
@@ -38,25 +39,10 @@ __device__ __forceinline__ bool list_entry_valid(int32_t j, int32_t n_v,
 // ---------------------------------------------------------------------------------------
 // als_list_exposure
 // ---------------------------------------------------------------------------------------
-constexpr int kLxWindow = 8192;        // LDS counters (and tags) per workgroup; a power of two
+// (the cache itself, kLxWindow slots claimed and added to by lx_add: lx_cache.h)
 constexpr int kLxThreads = 1024;
 constexpr int kLxMaxBlocks = 512;      // two workgroups per compute unit
 constexpr int kLxChunkEntries = 16384; // list slots a workgroup takes at a time
-
-// One entry of row `key`: an LDS add when the row owns (or can claim) its slot, a global add
-// otherwise.  (One global add per entry, and this cache behind a per-wave fold of equal keys,
-// were measured and are not kept: DESIGN.md section K15.)
-__device__ __forceinline__ void lx_add(int32_t key, int32_t* __restrict__ scnt,
-                                       int32_t* __restrict__ stag, int32_t* __restrict__ counts) {
-  const int slot = key & (kLxWindow - 1);
-  int32_t tag = __atomic_load_n(&stag[slot], __ATOMIC_RELAXED);
-  if (tag < 0) {
-    const int32_t old = atomicCAS(&stag[slot], -1, key);
-    tag = old < 0 ? key : old;
-  }
-  if (tag == key) atomicAdd(&scnt[slot], 1);
-  else atomicAdd(&counts[key], 1);
-}
 
 // Rows go through in chunks of rows_per_chunk (rows_per_chunk * at < 2^31, so a slot's row and
 // position come from one 32-bit division); workgroups stride over the chunks.
@@ -67,10 +53,7 @@ __global__ __launch_bounds__(kLxThreads) void list_exposure_kernel(
   __shared__ int32_t scnt[kLxWindow];
   __shared__ int32_t stag[kLxWindow];
   __shared__ unsigned long long sskip;
-  for (int s = threadIdx.x; s < kLxWindow; s += kLxThreads) {
-    scnt[s] = 0;
-    stag[s] = -1;
-  }
+  lx_clear<kLxThreads>(scnt, stag);
   if (threadIdx.x == 0) sskip = 0ull;
   __syncthreads();
   unsigned long long skipped = 0ull;
@@ -89,10 +72,7 @@ __global__ __launch_bounds__(kLxThreads) void list_exposure_kernel(
   }
   if (skipped) atomicAdd(&sskip, skipped);
   __syncthreads();
-  for (int s = threadIdx.x; s < kLxWindow; s += kLxThreads) {
-    const int32_t c = scnt[s];
-    if (c) atomicAdd(&counts[stag[s]], c);
-  }
+  lx_flush<kLxThreads>(scnt, stag, counts);
   if (threadIdx.x == 0 && n_skipped && sskip) atomicAdd(n_skipped, sskip);
 }
 

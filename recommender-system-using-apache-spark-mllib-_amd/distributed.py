@@ -44,7 +44,7 @@ import torch
 import torch.distributed as dist
 
 from .kernels.csr import id_offset
-from .filters import (reject_sharded_diversify, reject_sharded_explain, reject_sharded_filters,
+from .filters import (reject_sharded_co_rated, reject_sharded_diversify, reject_sharded_explain, reject_sharded_filters,
                       reject_sharded_fold_in,
                       reject_sharded_full_rank, reject_sharded_list_metrics,
                       reject_sharded_nonnegative,
@@ -1015,6 +1015,16 @@ class ShardedALS:
                      sweeps: int = 10):
         """ALSCore.fit_baseline is not offered on the sharded engine yet."""
         reject_sharded_rating_stats()
+
+    def co_rated(self, ids, top: int, user_side: bool = False, *, measure: str = "jaccard",
+                 min_common: int = 1, candidates=None):
+        """ALSCore.co_rated is not offered on the sharded engine yet."""
+        reject_sharded_co_rated()
+
+    def co_rated_all(self, top: int, user_side: bool = False, *, measure: str = "jaccard",
+                     min_common: int = 1, candidates=None):
+        """ALSCore.co_rated_all is not offered on the sharded engine yet."""
+        reject_sharded_co_rated()
 
     def add_ratings(self, users, items, ratings, *, seed=0) -> dict:
         """ALSCore.add_ratings is not offered on the sharded engine yet."""

@@ -62,6 +62,10 @@ from .kernels.stats import (
     RATING_MOMENTS, BASELINE_METHODS, rating_stats_task, rating_stats_group_rows, row_moments,
     bias_update, baseline_predict_rows, rating_stats_dict, Baseline,
 )
+from .kernels.co_rated import (
+    CO_RATED_MEASURES, CO_RATED_MAX_TOP, CO_RATED_PASS, CO_RATED_MAX_PASS, co_rated_task,
+    co_rated_window, co_rated_rows,
+)
 
 
 def make_engine(users, items, ratings, device=None):
@@ -1526,6 +1530,55 @@ class ALSCore:
                                      + reg_item * (bi * bi).sum()))
         return Baseline(method, mu, bu, bi, self.uidx, self.iidx, history, self.ws,
                         reg_user, reg_item)
+
+    # ---- K19: which rows were rated together with this one? ----
+    def _co_rated_args(self, top, user_side: bool, measure, min_common, candidates, what: str):
+        """(index, queried block, other block, t, allow mask) of a co-rated search."""
+        top = int(top)
+        if not 1 <= top <= CO_RATED_MAX_TOP:
+            raise ValueError(f"top must be in [1, {CO_RATED_MAX_TOP}], got {top}")
+        if measure not in CO_RATED_MEASURES:
+            raise ValueError(f"measure must be one of {CO_RATED_MEASURES}, got {measure!r}")
+        if int(min_common) < 1:
+            raise ValueError(f"min_common must be >= 1, got {min_common}")
+        mine = self._stats_block(user_side, what)
+        other = self._stats_block(not user_side, what)
+        qi = self.uidx if user_side else self.iidx
+        return qi, mine, other, top, self._allow_bits(qi, candidates)
+
+    def co_rated(self, ids, top: int, user_side: bool = False, *, measure: str = "jaccard",
+                 min_common: int = 1, candidates=None):
+        """Co-rated neighbours from the training ratings themselves (K19, als_co_rated): for
+        the distinct known ids of `ids` (ascending; unknown ids dropped, as similar drops
+        them) the `top` OTHER rows of the same side that share the most raters with it —
+        "who rated X also rated Y" for items (the default), "who rated what I rated" for
+        users.  With n_a the ratings of row a and c the ratings the pair shares (rows of the
+        other side that rated both; duplicate ratings count with their multiplicity),
+        measure is "count" (c), "jaccard" (c / (n_a + n_b - c)) or "cosine" (c / sqrt(n_a
+        n_b)); rating values are not used.  A row is listed when c >= min_common and it is
+        among `candidates` (ids of the same side; None = all).  Returns (keys [m], ids [m, t],
+        scores [m, t], common [m, t]) on the device, t = top, score descending, ties by
+        ascending dense row; slots past a row's neighbours have score -inf and common 0.
+        Exact: only integers are summed.  Needs the ratings (not a from_factors core)."""
+        qi, mine, other, t, bits = self._co_rated_args(top, user_side, measure, min_common,
+                                                       candidates, "co_rated")
+        keys, rows = self._known_rows(qi, ids)
+        idx, sc, common = co_rated_rows(mine, other, rows, t, measure, min_common, bits, self.ws)
+        return keys, ids_of(qi.ids(), idx), sc, common
+
+    def co_rated_all(self, top: int, user_side: bool = False, *, measure: str = "jaccard",
+                     min_common: int = 1, candidates=None):
+        """co_rated for every row of the side, in dense order: (keys [n], ids [n, t], scores
+        [n, t], common [n, t]); the rows go through the kernel in passes of CO_RATED_PASS.
+        Cost: counting walks, for every row of the other side, its ratings once per rating
+        it holds — sum over those rows of len^2 integer adds; ranking reads the n counters
+        of each of the n queries, n^2 overall.  That suits a catalogue of 10^4 - 10^5 rows
+        (the item side), not a side of 10^7 users."""
+        qi, mine, other, t, bits = self._co_rated_args(top, user_side, measure, min_common,
+                                                       candidates, "co_rated_all")
+        rows = torch.arange(qi.n, dtype=torch.int32, device=self.device)
+        idx, sc, common = co_rated_rows(mine, other, rows, t, measure, min_common, bits, self.ws)
+        return qi.ids(), ids_of(qi.ids(), idx), sc, common
 
     def recommend_users(self, top: int):
         """For every user (dense order): top items as (item ids, scores)."""

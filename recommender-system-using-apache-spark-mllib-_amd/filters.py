@@ -204,6 +204,15 @@ def reject_sharded_rating_stats() -> None:
         "single-GPU engine, an ALSCore built on the same ratings")
 
 
+def reject_sharded_co_rated() -> None:
+    """The sharded engine carries co_rated / co_rated_all with the single-GPU signature and
+    refuses them, as it refuses rating_stats."""
+    raise NotImplementedError(
+        "co_rated / co_rated_all are not supported by the sharded engine (ShardedALS) yet: "
+        "co-rated neighbours run on the single-GPU engine, an ALSCore built on the same "
+        "ratings")
+
+
 def reject_sharded_regression() -> None:
     """The sharded engine carries regression_metrics with the single-GPU signature and
     refuses it, as it refuses rank_metrics."""

@@ -716,6 +716,76 @@ class ALSModel:
         return self._similar_df(col, *self._core.similar_all(int(numItems), False,
                                                              candidates=candidates))
 
+    # -- co-rated neighbours (K19): "who rated X also rated Y", from the ratings themselves --
+    @staticmethod
+    def _co_rated_df(key_col, keys, ids, sc, common):
+        import pandas as pd
+        keys, ids = keys.cpu().numpy(), ids.cpu().numpy()
+        sc, common = sc.cpu().numpy(), common.cpu().numpy()
+        rows = [[(int(a), float(b)) for a, b, c in zip(ri, rs, rc) if c > 0]
+                for ri, rs, rc in zip(ids, sc, common)]
+        counts = [[int(c) for c in rc if c > 0] for rc in common]
+        return pd.DataFrame({key_col: keys, "similar": rows, "common": counts})
+
+    def _co_rated(self, dataset_or_ids, num, user_side: bool, measure, minCommon, candidates):
+        col = self._p["userCol" if user_side else "itemCol"]
+        if candidates is not None:
+            candidates = check_integers(np.asarray(candidates).reshape(-1), col)
+        return self._co_rated_df(col, *self._core.co_rated(
+            self._similar_ids(dataset_or_ids, col), int(num), user_side, measure=measure,
+            min_common=int(minCommon), candidates=candidates))
+
+    def coRatedItems(self, dataset_or_ids, numItems: int, measure: str = "jaccard",
+                     minCommon: int = 1, candidates=None):
+        """"Who rated this item also rated": DataFrame[itemCol, similar: list of (item, score),
+        common: list of shared-rater counts] for the distinct known items of
+        `dataset_or_ids` (as similarItems reads them): the numItems items that share the most
+        raters with each in the training ratings, strongest first (ties: lower dense row
+        first).  measure: "count" (c), "jaccard" (c / (n_a + n_b - c)) or "cosine"
+        (c / sqrt(n_a n_b)) of the two rater sets; an item is listed from minCommon shared
+        raters and, with candidates=, only when it is among those ids.  Counted from the
+        ratings, exactly (K19); the factors are not used, so this is the yardstick the
+        factor neighbours of similarItems can be held against (neighbourAgreement).  Raises
+        ValueError on a loaded model, which holds no ratings."""
+        return self._co_rated(dataset_or_ids, numItems, False, measure, minCommon, candidates)
+
+    def coRatedUsers(self, dataset_or_ids, numUsers: int, measure: str = "jaccard",
+                     minCommon: int = 1, candidates=None):
+        """coRatedItems among the users: DataFrame[userCol, similar, common], common = the
+        items both rated."""
+        return self._co_rated(dataset_or_ids, numUsers, True, measure, minCommon, candidates)
+
+    def coRatedItemsForAllItems(self, numItems: int, measure: str = "jaccard", minCommon: int = 1,
+                                candidates=None):
+        """coRatedItems for every item of the model (ALSCore.co_rated_all, which states the
+        cost: quadratic in the catalogue)."""
+        col = self._p["itemCol"]
+        if candidates is not None:
+            candidates = check_integers(np.asarray(candidates).reshape(-1), col)
+        return self._co_rated_df(col, *self._core.co_rated_all(
+            int(numItems), False, measure=measure, min_common=int(minCommon),
+            candidates=candidates))
+
+    def neighbourAgreement(self, dataset_or_ids, numItems: int) -> float:
+        """How far the factors learnt what the ratings say: the mean over the distinct known
+        items of `dataset_or_ids` of |similarItems ∩ coRatedItems| / numItems (both lists of
+        numItems, coRatedItems at its defaults), in [0, 1]; NaN when no item is known."""
+        col = self._p["itemCol"]
+        ids = self._similar_ids(dataset_or_ids, col)
+        num = int(numItems)
+        _, a, sa = self._core.similar(ids, num, False)
+        _, b, _, cb = self._core.co_rated(ids, num, False)
+        return self._list_agreement(a, torch.isfinite(sa), b, cb > 0, num)
+
+    @staticmethod
+    def _list_agreement(a, a_ok, b, b_ok, num: int) -> float:
+        """Mean over rows of |{a[r, i]: a_ok} ∩ {b[r, j]: b_ok}| / num for two id tables with
+        one row per query (ids distinct within a row)."""
+        if a.shape[0] == 0:
+            return float("nan")
+        hit = (a.unsqueeze(2) == b.unsqueeze(1)) & a_ok.unsqueeze(2) & b_ok.unsqueeze(1)
+        return float(hit.any(2).sum(1).double().mean() / num)
+
     def recommendForItemSubset(self, dataset, numUsers: int, *, exclude=None, candidates=None):
         col = self._p["itemCol"]
         ids = check_integers(columns_of(dataset, (col,))[0], col)

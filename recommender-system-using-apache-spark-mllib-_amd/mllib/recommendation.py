@@ -231,6 +231,33 @@ class MatrixFactorizationModel:
         """similarProducts among the user factors: [(user, similarity)]."""
         return self._similar_one(int(user), num, True, candidates)
 
+    def _co_rated_one(self, key, num, user_side, measure, minCommon, candidates):
+        if candidates is not None:
+            candidates = check_integers(np.asarray(candidates).reshape(-1),
+                                        "user" if user_side else "product")
+        keys, ids, sc, common = self._core.co_rated([int(key)], int(num), user_side,
+                                                    measure=measure, min_common=int(minCommon),
+                                                    candidates=candidates)
+        if keys.numel() == 0:
+            raise KeyError(f"unknown id {key}")
+        ids, sc, common = ids.cpu().numpy()[0], sc.cpu().numpy()[0], common.cpu().numpy()[0]
+        return [(int(a), float(s), int(c)) for a, s, c in zip(ids, sc, common) if c > 0]
+
+    def coRatedProducts(self, product: int, num: int, *, measure: str = "jaccard",
+                        minCommon: int = 1, candidates=None):
+        """"Who rated this also rated": the `num` products that share the most raters with
+        `product` in the training ratings, [(product, score, common raters)], strongest first
+        (K19; exact integer counts, the factors are not used).  measure: "count", "jaccard"
+        or "cosine" of the two rater sets; a product is listed from minCommon shared raters
+        and, with candidates=, only when it is among those ids.  KeyError for an unknown
+        product; ValueError on a loaded model, which holds no ratings."""
+        return self._co_rated_one(int(product), num, False, measure, minCommon, candidates)
+
+    def coRatedUsers(self, user: int, num: int, *, measure: str = "jaccard", minCommon: int = 1,
+                     candidates=None):
+        """coRatedProducts among the users: [(user, score, products both rated)]."""
+        return self._co_rated_one(int(user), num, True, measure, minCommon, candidates)
+
     def recommendProductsForUsers(self, num: int, *, exclude=None, candidates=None):
         keys, ids, sc = self._core.recommend_all(int(num), True,
                                                  **self._filters(exclude, candidates, True))

@@ -22,7 +22,7 @@ import numpy as np
 
 __all__ = ["movie_counts_and_averages", "highest_rated_movies", "personal_recommendations",
            "personal_recommendations_fold_in", "personal_recommendations_update",
-           "personal_explanations", "similar_movies"]
+           "personal_explanations", "similar_movies", "also_rated_movies"]
 
 
 def movie_counts_and_averages(ratings) -> Dict[int, Tuple[int, float]]:
@@ -190,6 +190,39 @@ def similar_movies(model, movie_ids: Iterable[int], movies: Iterable[Sequence], 
     name = lambda a: titles.get(int(a), str(int(a)))
     return [(name(k), [(name(a), float(s)) for a, s in zip(ri, rs) if np.isfinite(s)])
             for k, ri, rs in zip(keys, ids, sc)]
+
+
+def also_rated_movies(model, movies: Iterable[Sequence], movie_id: int, num: int = 10,
+                      min_ratings: int = 0, measure: str = "jaccard"
+                      ) -> List[Tuple[float, str, int, int]]:
+    """"People who rated this movie also rated": (score, movie name, raters in common, number
+    of ratings) of the `num` movies that share the most raters with `movie_id` in the ratings
+    the model was fitted on, strongest first (K19, ALSCore.co_rated: counted from the
+    ratings, the factors are not used).
+
+    movies: (MovieID, title) pairs; a movie without a title is named by its id
+    min_ratings: only movies with MORE than min_ratings training ratings are listed (the
+        reference's R:245 filter, applied to the neighbours as similar_movies applies it);
+        the queried movie itself need not pass it
+    measure: "count", "jaccard" or "cosine" of the two rater sets
+    An unknown movie_id gives []."""
+    titles = {}
+    for m, t in movies:
+        titles.setdefault(int(m), str(t))
+    if not -(2 ** 31) <= int(movie_id) < 2 ** 31:
+        return []
+    eng = _engine_of(model)
+    st = eng.rating_stats(user_side=False)
+    ids, counts = st["ids"].cpu().numpy(), st["count"].cpu().numpy()
+    n_of = dict(zip(ids.tolist(), counts.tolist()))
+    cand = ids[counts > int(min_ratings)].astype(np.int32)
+    keys, nb, sc, common = (x.cpu().numpy() for x in eng.co_rated(
+        np.asarray([int(movie_id)], np.int32), int(num), False, measure=measure,
+        candidates=cand))
+    if len(keys) == 0:
+        return []
+    return [(float(s), titles.get(int(a), str(int(a))), int(c), int(n_of[int(a)]))
+            for a, s, c in zip(nb[0], sc[0], common[0]) if c > 0]
 
 
 def personal_recommendations_update(model, user_id: int, rated: Iterable[Sequence],
