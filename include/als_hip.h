@@ -962,6 +962,87 @@ int als_co_rated(const int64_t* row_ptr_q, const int32_t* col_q, int64_t n,
                  int32_t* idx, float* score, int32_t* common,
                  void* ws, size_t ws_bytes, void* stream);
 
+/* ---- K20: per-user holdout and stratified folds (leave-k-out, the protocol HR@k, NDCG@k and
+ *      MRR are reported under; Spark's randomSplit is a global row split) -------------------- */
+
+/* Added under ABI 9 without a version bump: six new symbols only, nothing existing changes.
+ * Which stored entries of a built rating set are held out, from (seed, user id, item id), the
+ * rows' eligible sets and a rank window per row; the answer is keep bits in K18's format, so
+ * als_csr_remove_compact makes the training side and, from the complement, the held-out triples.
+ *   a side      row_ptr int64 [n_rows + 1], col int32 [nnz] (dense rows of the other side, n_cols
+ *               of them), row_ids int32 [n_rows] and col_ids int32 [n_cols] the EXTERNAL ids of
+ *               the dense rows of this and of the other side; rows_are_users != 0 when this
+ *               side's rows are the users
+ *   key         (seed: the 64 bits of the int64 argument, as uint64) splitmix64 of x =
+ *               (uint64(uint32(user id)) << 32) | uint32(item id):
+ *                 z = x + (seed + 1) * 0x9E3779B97F4A7C15
+ *                 z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *                 z = (z ^ (z >> 27)) * 0x94D049BB133111EB,  key = z ^ (z >> 31)   (mod 2^64)
+ *   composite   (key, column), compared lexicographically; "the end" is (2^64 - 1, 2^31 - 1),
+ *               above every composite of a stored entry
+ * One side SELECTS (its rows have the windows: the users, for a per-user holdout).
+ * als_split_anchor runs on the OTHER side and writes
+ *   anchor      int32 [n_rows]: the column (a dense row of the selecting side) of the row's
+ *               smallest composite, -1 for a row without entries.  The entries (anchor[i], i) —
+ *               every stored copy — are not eligible, so no row of the other side loses its last
+ *               rating.  A wavefront per row; a row of more than 2048 entries is cut into tiles
+ *               whose partial minima go through `scratch` and are merged by the row's wavefront
+ * als_split_eligible runs on the selecting side and writes
+ *   eligible    int32 [n_rows]: the row's entries that are no anchor (anchor int32 [n_cols], as
+ *               als_split_anchor wrote it, or NULL: every entry is eligible).  The caller makes
+ *               the windows from it
+ * als_split_thresholds runs on the selecting side.  The rank of an eligible entry is the number
+ * of eligible entries of its row with a strictly smaller composite, so stored copies of a pair
+ * share a rank.  With win_lo, win_hi int32 [n_rows] (a negative rank counts as 0) it writes
+ *   thr_lo_key uint64 [n_rows], thr_lo_col int32 [n_rows]: the smallest composite among the
+ *               row's eligible entries of rank >= win_lo[r], the end when there is none (always
+ *               when win_lo[r] >= eligible[r]); thr_hi_* the same for win_hi.  An eligible entry
+ *               has win_lo <= rank < win_hi exactly when thr_lo <= its composite < thr_hi
+ *   row_cap     rows of at most row_cap entries (0 = als_split_row_cap(), the largest allowed)
+ *               are ranked by one wavefront with the row's composites in LDS, four rows per
+ *               workgroup; longer rows are listed in `scratch` and a workgroup per listed row
+ *               selects by radix on the key's bytes (eight histogram passes, both ranks at once)
+ *               and resolves ties on (key, column) exactly.  No limit on the row length; a small
+ *               row_cap exists so that tests reach the long-row path with short rows.  The
+ *               outputs do not depend on row_cap
+ * als_split_mark runs on EITHER side (selecting != 0: this side's rows have the thresholds and
+ * `anchor` is indexed by its columns; selecting == 0: the thresholds are indexed by this side's
+ * columns, `anchor` by its rows, and the composite's column is this side's row) and writes
+ *   keep_bits, tile_off, row_ptr_kept   exactly as als_csr_remove_mark does, with "stays" =
+ *               not (eligible and thr_lo <= composite < thr_hi), tiles of als_csr_remove_tile()
+ *               entries.  Both sides mark by one predicate of the pair, so they keep the same
+ *               ratings: no delete list, no sort, no host read
+ * Scratch: als_split_scratch_bytes(nnz, n_rows) bytes for the side passed, 8-byte aligned; it
+ * need not be initialised and no result depends on what it or the outputs held before.  Integer
+ * work only; the atomics are integer adds and minima, so two calls give identical bytes.  A
+ * column outside [0, n_cols) is never used as an index: the entry is no anchor, not eligible, and
+ * stays.  Row positions are clamped to [0, nnz].
+ * Checked on the host before any launch: a negative size and a null pointer that would be read
+ * or written are ALS_EINVAL, as is row_cap outside [0, als_split_row_cap()]; nnz >= 2^31 or a
+ * side of 2^31 - 1 rows (K1's limit) ALS_EUNSUPPORTED; a short scratch ALS_EWORKSPACE.
+ * Cost beside the host split it replaces: DESIGN.md section K20. */
+int32_t als_split_row_cap(void);
+size_t als_split_scratch_bytes(int64_t nnz, int32_t n_rows);
+int als_split_anchor(const int64_t* row_ptr, const int32_t* col, int64_t nnz, int32_t n_rows,
+                     int32_t n_cols, const int32_t* row_ids, const int32_t* col_ids,
+                     int32_t rows_are_users, int64_t seed, int32_t* anchor, void* scratch,
+                     size_t scratch_bytes, void* stream);
+int als_split_eligible(const int64_t* row_ptr, const int32_t* col, int64_t nnz, int32_t n_rows,
+                       int32_t n_cols, const int32_t* anchor, int32_t* eligible, void* stream);
+int als_split_thresholds(const int64_t* row_ptr, const int32_t* col, int64_t nnz, int32_t n_rows,
+                         int32_t n_cols, const int32_t* row_ids, const int32_t* col_ids,
+                         int32_t rows_are_users, int64_t seed, const int32_t* anchor,
+                         const int32_t* win_lo, const int32_t* win_hi, int32_t row_cap,
+                         uint64_t* thr_lo_key, int32_t* thr_lo_col, uint64_t* thr_hi_key,
+                         int32_t* thr_hi_col, void* scratch, size_t scratch_bytes, void* stream);
+int als_split_mark(const int64_t* row_ptr, const int32_t* col, int64_t nnz, int32_t n_rows,
+                   int32_t n_cols, const int32_t* row_ids, const int32_t* col_ids,
+                   int32_t rows_are_users, int64_t seed, int32_t selecting,
+                   const uint64_t* thr_lo_key, const int32_t* thr_lo_col,
+                   const uint64_t* thr_hi_key, const int32_t* thr_hi_col, const int32_t* anchor,
+                   uint64_t* keep_bits, int64_t* tile_off, int64_t* row_ptr_kept, void* scratch,
+                   size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,14 @@ SIGNATURES = {
     "als_co_rated_scratch_bytes": (SZ, [I64, I32, I32, I32]),
     "als_co_rated": (ctypes.c_int, [P, P, I64, P, P, I64, P, I32, I32, I32, P, I32, I32, I32, P, P,
                                     P, P, SZ, P]),
+    "als_split_row_cap": (I32, []),
+    "als_split_scratch_bytes": (SZ, [I64, I32]),
+    "als_split_anchor": (ctypes.c_int, [P, P, I64, I32, I32, P, P, I32, I64, P, P, SZ, P]),
+    "als_split_eligible": (ctypes.c_int, [P, P, I64, I32, I32, P, P, P]),
+    "als_split_thresholds": (ctypes.c_int, [P, P, I64, I32, I32, P, P, I32, I64, P, P, P, I32, P,
+                                            P, P, P, P, SZ, P]),
+    "als_split_mark": (ctypes.c_int, [P, P, I64, I32, I32, P, P, I32, I64, I32, P, P, P, P, P, P,
+                                      P, P, P, SZ, P]),
 }
 
 ABI_VERSION = 9

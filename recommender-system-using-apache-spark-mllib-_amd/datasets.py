@@ -90,6 +90,28 @@ def random_split(n: int, weights=(6, 2, 2), seed: int = 0):
     return [np.nonzero(bins == b)[0] for b in range(len(weights))]
 
 
+def core_triples(core):
+    """The ratings an ALSCore holds as (users int32, items int32, ratings f32) device tensors
+    with external ids, in the user side's stored order (users ascending, a user's ratings in
+    input order)."""
+    b = core.user_block
+    users = torch.repeat_interleave(core.uidx.ids(), b.row_ptr[1:] - b.row_ptr[:-1])
+    return users.contiguous(), core.iidx.ids()[b.col.long()].contiguous(), b.val
+
+
+def user_holdout_split(users, items, ratings, *, count=None, fraction=None, seed: int = 0,
+                       min_keep: int = 1, keep_items: bool = True, device=None):
+    """Per-user holdout for callers without a core: ((train users, items, ratings), (test
+    users, items, ratings)), device tensors, both in the user side's stored order.  Of every
+    user `count` ratings (count=1: leave-one-out) or the share `fraction` go to the test
+    part, chosen by ALSCore.split's rule from (seed, user id, item id) on the GPU; with
+    keep_items no item leaves the training part, so no test pair is cold."""
+    from .engine import ALSCore
+    train, held = ALSCore(users, items, ratings, device=device).split(
+        count=count, fraction=fraction, seed=seed, min_keep=min_keep, keep_items=keep_items)
+    return core_triples(train), held
+
+
 # ---------------------------------------------------------------- synthetic
 CONFIGS = {
     # name: (n_users, n_items, nnz, half_stars, data_seed)

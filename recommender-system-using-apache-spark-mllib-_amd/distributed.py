@@ -50,7 +50,8 @@ from .filters import (reject_sharded_co_rated, reject_sharded_diversify, reject_
                       reject_sharded_nonnegative,
                       reject_sharded_objective, reject_sharded_rating_stats,
                       reject_sharded_regression,
-                      reject_sharded_remove, reject_sharded_similar, reject_sharded_update)
+                      reject_sharded_remove, reject_sharded_similar, reject_sharded_split,
+                      reject_sharded_update)
 
 
 class HipKernels:
@@ -1053,6 +1054,16 @@ class ShardedALS:
     def set_ratings(self, users, items, ratings, *, seed=0) -> dict:
         """ALSCore.set_ratings is not offered on the sharded engine yet."""
         reject_sharded_remove()
+
+    def holdout(self, *, count=None, fraction=None, fold=None, seed=0, min_keep=1,
+                keep_items=True, user_side=True):
+        """ALSCore.holdout is not offered on the sharded engine yet."""
+        reject_sharded_split()
+
+    def split(self, *, count=None, fraction=None, fold=None, seed=0, min_keep=1,
+              keep_items=True, user_side=True):
+        """ALSCore.split is not offered on the sharded engine yet."""
+        reject_sharded_split()
 
     def regression_metrics(self, users, items, ratings, through_origin: bool = False) -> dict:
         """ALSCore.regression_metrics is not offered on the sharded engine yet."""

@@ -62,6 +62,10 @@ from .kernels.stats import (
     RATING_MOMENTS, BASELINE_METHODS, rating_stats_task, rating_stats_group_rows, row_moments,
     bias_update, baseline_predict_rows, rating_stats_dict, Baseline,
 )
+from .kernels.split import (
+    SPLIT_MODES, split_row_cap, split_anchor, split_eligible, split_thresholds, split_mark,
+    check_split_args, split_windows,
+)
 from .kernels.co_rated import (
     CO_RATED_MEASURES, CO_RATED_MAX_TOP, CO_RATED_PASS, CO_RATED_MAX_PASS, co_rated_task,
     co_rated_window, co_rated_rows,
@@ -650,6 +654,54 @@ class ALSCore:
             raise RuntimeError(f"{who}: the two sides disagree on what stays")
         return mu, mi, mu[3], nnz
 
+    def _kept_state(self, mu, mi, nnz, blocks_only: bool = False) -> dict:
+        """remove_ratings steps c and d for the two sides' K18-format marks (keep_bits,
+        tile_off, row_ptr_kept, ...) that keep `nnz` ratings, storing nothing: the shrunk id
+        maps, the compacted CSR sides and the moved factor rows.  blocks_only: neither the
+        factor rows nor the touched rows are made (split's new core has no use for them)."""
+        ub, ib = self.user_block, self.item_block
+        side = []
+        for block, idx, marks in ((ub, self.uidx, mu), (ib, self.iidx, mi)):
+            kept = marks[2][1:] - marks[2][:-1]
+            had = block.row_ptr[1:] - block.row_ptr[:-1]
+            left = (kept == 0).nonzero().flatten()
+            shrunk, mp = shrink_index(idx, left, self.ws)
+            touched = None
+            if not blocks_only:
+                changed = ((kept > 0) & (kept < had)).nonzero().flatten()
+                touched = changed if mp is None else mp[changed].long()
+            side.append(dict(idx=shrunk, map=mp, left=idx.ids()[left], kept=kept,
+                             touched=touched))
+        su, si = side
+        csr = []
+        for block, marks, me, other, n_cols in ((ub, mu, su, si, ib.n_rows),
+                                                (ib, mi, si, su, ub.n_rows)):
+            col, val = remove_compact(block.col, block.val, marks[0], marks[1], other["map"],
+                                      n_cols, nnz)
+            stays = torch.ones(block.n_rows + 1, dtype=torch.bool, device=self.device)
+            stays[:-1] = me["kept"] > 0               # the last word is nnz
+            csr.append((marks[2][stays].contiguous(), col, val))
+        U = V = None
+        if not blocks_only and self.rank > 0 and self.U is not None:
+            U = self.U if su["map"] is None else self.U[su["kept"] > 0].contiguous()
+            V = self.V if si["map"] is None else self.V[si["kept"] > 0].contiguous()
+        return dict(su=su, si=si, csr=csr, U=U, V=V, nnz=nnz)
+
+    def _kept_commit(self, st: dict) -> None:
+        """Store what _kept_state made (remove_ratings steps d's scheduling and e): nothing
+        before this touched the core, and from here on it cannot fail half-way."""
+        su, si, csr, nnz = st["su"], st["si"], st["csr"], st["nnz"]
+        ub, ib = self.user_block, self.item_block
+        self.user_block = schedule_block(su["idx"].n, nnz, *csr[0], self.ws, ub.chunk)
+        self.item_block = schedule_block(si["idx"].n, nnz, *csr[1], self.ws, ib.chunk)
+        self.nnz = nnz
+        self.uidx, self.iidx = su["idx"], si["idx"]
+        if st["U"] is not None:
+            self.U, self.V = st["U"], st["V"]
+        self._train_ex = {}
+        self.ws.rating_scale_key = None   # the largest |rating| may have left
+        self._retouch((su["map"], si["map"]), (su["touched"], si["touched"]))
+
     def remove_ratings(self, users, items) -> dict:
         """Take ratings back from the core in place: every stored copy of every listed (user,
         item) pair goes (a pair listed twice is listed once).  After the call every
@@ -695,39 +747,10 @@ class ALSCore:
             return info
         if nnz == 0:
             raise ValueError("remove_ratings would remove every rating: a model needs one")
-        ub, ib = self.user_block, self.item_block
-        side = []
-        for block, idx, marks in ((ub, self.uidx, mu), (ib, self.iidx, mi)):
-            kept = marks[2][1:] - marks[2][:-1]
-            had = block.row_ptr[1:] - block.row_ptr[:-1]
-            left = (kept == 0).nonzero().flatten()
-            shrunk, mp = shrink_index(idx, left, self.ws)
-            changed = ((kept > 0) & (kept < had)).nonzero().flatten()
-            side.append(dict(idx=shrunk, map=mp, left=idx.ids()[left], kept=kept,
-                             touched=changed if mp is None else mp[changed].long()))
-        su, si = side
-        csr = []
-        for block, marks, me, other, n_cols in ((ub, mu, su, si, ib.n_rows),
-                                                (ib, mi, si, su, ub.n_rows)):
-            col, val = remove_compact(block.col, block.val, marks[0], marks[1], other["map"],
-                                      n_cols, nnz)
-            stays = torch.ones(block.n_rows + 1, dtype=torch.bool, device=self.device)
-            stays[:-1] = me["kept"] > 0               # the last word is nnz
-            csr.append((marks[2][stays].contiguous(), col, val))
-        U = V = None
-        if self.rank > 0 and self.U is not None:
-            U = self.U if su["map"] is None else self.U[su["kept"] > 0].contiguous()
-            V = self.V if si["map"] is None else self.V[si["kept"] > 0].contiguous()
-        # nothing above touched the core: from here on it cannot fail half-way
-        self.user_block = schedule_block(su["idx"].n, nnz, *csr[0], self.ws, ub.chunk)
-        self.item_block = schedule_block(si["idx"].n, nnz, *csr[1], self.ws, ib.chunk)
-        removed, self.nnz = self.nnz - nnz, nnz
-        self.uidx, self.iidx = su["idx"], si["idx"]
-        if U is not None:
-            self.U, self.V = U, V
-        self._train_ex = {}
-        self.ws.rating_scale_key = None   # the largest |rating| may have left
-        self._retouch((su["map"], si["map"]), (su["touched"], si["touched"]))
+        st = self._kept_state(mu, mi, nnz)
+        removed = self.nnz - nnz
+        self._kept_commit(st)
+        su, si = st["su"], st["si"]
         info.update(removed=removed,
                     missing=int(u.numel()) - int(known.sum()) + int((hits == 0).sum()),
                     left_users=su["left"], left_items=si["left"], touched_users=su["touched"],
@@ -795,6 +818,117 @@ class ALSCore:
         info = self._add_commit(self._add_compute(u, i, r, seed, ucsr, icsr, nnz))
         info["replaced"] = replaced
         return info
+
+    # ---- K20: per-user holdout and stratified folds ----
+    def _split_marks(self, count, fraction, fold, seed, min_keep, keep_items, user_side,
+                     row_cap: int = 0):
+        """K20's four calls: (user marks, item marks, the ratings that stay)."""
+        mode, value = check_split_args(count, fraction, fold, min_keep)
+        ub, ib = self.user_block, self.item_block
+        uids, iids = self.uidx.ids().contiguous(), self.iidx.ids().contiguous()
+        sel, oth = (ub, ib) if user_side else (ib, ub)
+        sel_ids, oth_ids = (uids, iids) if user_side else (iids, uids)
+        anchor = None
+        if keep_items:
+            anchor = split_anchor(oth.row_ptr, oth.col, sel.n_rows, oth_ids, sel_ids,
+                                  not user_side, seed, self.ws)
+        e = split_eligible(sel.row_ptr, sel.col, oth.n_rows, anchor)
+        lo, hi = split_windows(e, mode, value, int(min_keep))
+        thr = split_thresholds(sel.row_ptr, sel.col, oth.n_rows, sel_ids, oth_ids, user_side,
+                               seed, anchor, lo, hi, self.ws, row_cap)
+        mu = split_mark(ub.row_ptr, ub.col, ib.n_rows, uids, iids, True, seed, user_side, thr,
+                        anchor, self.ws)
+        mi = split_mark(ib.row_ptr, ib.col, ub.n_rows, iids, uids, False, seed, not user_side,
+                        thr, anchor, self.ws)
+        nnz = int(mu[1][-1])
+        if nnz != int(mi[1][-1]):
+            raise RuntimeError("holdout: the two sides disagree on what stays")
+        return mu, mi, nnz
+
+    def _held_triples(self, mu, nnz):
+        """The held-out ratings from the user side's marks, in that side's stored order:
+        als_csr_remove_compact on the complement bits (tile_off of the complement = the tile's
+        start minus the kept offset, its row pointer = the old one minus the kept one)."""
+        ub = self.user_block
+        n_held = self.nnz - nnz
+        keep_bits, tile_off, row_ptr_kept = mu[:3]
+        T = csr_remove_tile()
+        start = torch.clamp(torch.arange(tile_off.numel(), device=self.device) * T, max=self.nnz)
+        col, val = remove_compact(ub.col, ub.val, ~keep_bits, start - tile_off, None,
+                                  self.item_block.n_rows, n_held)
+        gone = ub.row_ptr - row_ptr_kept
+        users = torch.repeat_interleave(self.uidx.ids(), gone[1:] - gone[:-1])
+        return users.contiguous(), self.iidx.ids()[col.long()].contiguous(), val
+
+    def _no_triples(self):
+        e = torch.empty(0, dtype=torch.int32, device=self.device)
+        return e, e.clone(), torch.empty(0, dtype=torch.float32, device=self.device)
+
+    def holdout(self, *, count=None, fraction=None, fold=None, seed=0, min_keep=1,
+                keep_items=True, user_side=True):
+        """Hold ratings of every user out of the core in place and return them: the split a
+        ranking metric needs (leave-k-out; HR@k, NDCG@k, MRR and the percentile rank are
+        reported under it).  Exactly one of
+          count=k          k ratings of every user (count=1 is leave-one-out),
+          fraction=p       round(p e) of a user's e eligible ratings,
+          fold=(f, F)      fold f of F stratified folds: every user's eligible ratings are cut
+                           into F parts whose sizes differ by at most one.
+        Which ratings go is a function of (seed, user id, item id) alone (a splitmix64 key per
+        pair, ranked within the user's eligible ratings; K20, include/als_hip.h): the same on
+        every run, whatever order the ratings were given in.  min_keep: count and fraction
+        leave a user at least this many eligible ratings.  keep_items: the rating of every
+        item with the smallest key is never held out, so no item leaves and no held-out pair
+        is cold.  user_side=False mirrors everything (per item; anchors protect users).
+        Stored copies of a pair go or stay together.
+        Afterwards the core is, bit for bit, what ALSCore(the kept triples in their original
+        order) holds, as after remove_ratings, and by the same tail: a row left without a
+        rating leaves, rows that stay keep their factors, the rows that lost ratings join
+        those refresh() re-solves.  Returns (users int32, items int32, ratings f32), the
+        held-out triples as device tensors with external ids, in the user side's stored
+        order; add_ratings(*held) puts them back.  A call that holds nothing out returns
+        empty tensors and changes nothing; one that would hold out everything raises
+        ValueError; nothing is changed when the call raises."""
+        self._need_ratings("holdout")
+        mu, mi, nnz = self._split_marks(count, fraction, fold, seed, min_keep, keep_items,
+                                        user_side)
+        if nnz == self.nnz:
+            return self._no_triples()
+        if nnz == 0:
+            raise ValueError("holdout would hold out every rating: a model needs one")
+        held = self._held_triples(mu, nnz)
+        self._kept_commit(self._kept_state(mu, mi, nnz))
+        return held
+
+    def split(self, *, count=None, fraction=None, fold=None, seed=0, min_keep=1,
+              keep_items=True, user_side=True):
+        """holdout() without touching this core: (train_core, (users, items, ratings)).  The
+        training core is a new unfitted ALSCore made of the compacted sides on the device (no
+        K1, no host copy) and equals ALSCore(the kept triples in their original order) bit for
+        bit; it shares nothing mutable with this core."""
+        self._need_ratings("split")
+        mu, mi, nnz = self._split_marks(count, fraction, fold, seed, min_keep, keep_items,
+                                        user_side)
+        if nnz == 0:
+            raise ValueError("split would hold out every rating: a model needs one")
+        held = self._held_triples(mu, nnz) if nnz != self.nnz else self._no_triples()
+        st = self._kept_state(mu, mi, nnz, blocks_only=True)
+        return self._from_blocks(st["su"]["idx"], st["si"]["idx"], st["csr"], nnz), held
+
+    def _from_blocks(self, uidx: IdIndex, iidx: IdIndex, csr, nnz: int) -> "ALSCore":
+        """An unfitted core over the given id maps and CSR sides ((row_ptr, col, val) of the
+        user and of the item side, device tensors the new core owns), scheduled as this core
+        is."""
+        core = ALSCore.__new__(ALSCore)
+        core._auto_chunk = self._auto_chunk
+        core.device = self.device
+        core.ws = Workspace(self.device, shared_rating_scale=True)
+        core.ws_yty = Workspace(self.device)
+        core.nnz = int(nnz)
+        core.uidx, core.iidx = uidx, iidx
+        core.user_block = schedule_block(uidx.n, nnz, *csr[0], core.ws, self.user_block.chunk)
+        core.item_block = schedule_block(iidx.n, nnz, *csr[1], core.ws, self.item_block.chunk)
+        core._blank_state()
+        return core
 
     def fingerprint(self) -> dict:
         """Order-independent identity of the training ratings (checkpoint matching)."""

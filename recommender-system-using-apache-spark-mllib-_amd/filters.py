@@ -186,6 +186,14 @@ def reject_sharded_update() -> None:
         "yet: ratings are added in place on the single-GPU engine, an ALSCore")
 
 
+def reject_sharded_split() -> None:
+    """The sharded engine carries holdout / split with the single-GPU signature and refuses
+    them, as it refuses remove_ratings."""
+    raise NotImplementedError(
+        "holdout / split are not supported by the sharded engine (ShardedALS) yet: the "
+        "per-user holdout is made on the single-GPU engine, an ALSCore")
+
+
 def reject_sharded_remove() -> None:
     """The sharded engine carries remove_ratings / remove_users / remove_items / set_ratings
     with the single-GPU signature and refuses them, as it refuses add_ratings."""

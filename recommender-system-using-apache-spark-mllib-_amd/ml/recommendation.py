@@ -227,6 +227,30 @@ class ALS(_Params):
         model._objective_every = self._objective_every or int(self._objective_tol is not None)
         return model
 
+    def fitHoldout(self, dataset, *, count: int = 1, k: int = 10, seed=None, exclude="train"):
+        """The usual leave-one-out report in one call: hold `count` ratings of every user out
+        (ALSCore.split on the GPU, K20: chosen from (seed, user id, item id), no item leaves
+        the training part), fit on the rest and score the held-out rows.  Returns (model,
+        metrics): the model fitted on the training part and evaluateRanking at k merged with
+        evaluateFullRanking (whose "rows" is kept as "fullRows"), both with `exclude`.  seed
+        None = this estimator's seed."""
+        _validate(self._p)
+        p = self._p
+        full = _engine.make_engine(*self._columns(dataset))
+        if not isinstance(full, _engine.ALSCore):
+            raise NotImplementedError("fitHoldout needs the single-GPU engine")
+        seed = (_DEFAULT_SEED if p["seed"] is None else int(p["seed"])) if seed is None else seed
+        core, held = full.split(count=int(count), seed=int(seed))
+        del full
+        model = ALSModel(self._fit_core(core), dict(p), solver=self._solver)
+        test = {c: x.cpu().numpy() for c, x in zip((p["userCol"], p["itemCol"], p["ratingCol"]),
+                                                   held)}
+        metrics = dict(model.evaluateRanking(test, int(k), exclude=exclude))
+        full_rank = model.evaluateFullRanking(test, exclude=exclude)
+        metrics.update({("fullRows" if key == "rows" else key): v
+                        for key, v in full_rank.items()})
+        return model, metrics
+
 
 _make_accessors(ALS, list(_Params._defaults))
 for _name in _Params._defaults:  # ALS.rank, als.regParam, ...: the keys of a param map

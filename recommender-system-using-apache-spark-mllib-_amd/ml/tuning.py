@@ -27,6 +27,14 @@ What differs from Spark, on purpose:
     silently).  With ALS the usual cause is coldStartStrategy="nan" and a validation row
     whose user or item is not in the training split: use coldStartStrategy="drop".
   * ``parallelism`` is accepted and ignored: the fits share one GPU and run in sequence.
+  * ``stratify="user"`` (not in Spark) splits per user on the GPU instead of per row on the
+    host (K20, ``ALSCore.split``): every user's validation share is 1 - trainRatio of their
+    ratings (or ``holdOut`` ratings: ``holdOut=1`` is leave-one-out), and a CrossValidator's
+    folds cut every user's ratings into numFolds parts whose sizes differ by at most one.
+    No item leaves a training part, so no validation pair is cold.  The full rating set is
+    built once; each training split is compacted from it on the device and is, bit for bit,
+    the engine a stand-alone fit on the kept rows would build.  ``stratify=None`` is the
+    host split described above, unchanged.
 """
 from __future__ import annotations
 
@@ -119,8 +127,9 @@ def _score(evaluator, model, validation) -> float:
     return float(evaluator.evaluate(model.transform(validation)))
 
 
-def _fit_and_score(estimator, maps, evaluator, train, validation, collect: bool):
-    """(metric per map, sub-model per map or None) of one training split."""
+def _fit_and_score(estimator, maps, evaluator, train, validation, collect: bool, core=None):
+    """(metric per map, sub-model per map or None) of one training split.  core: the
+    training engine of an ALS estimator when the caller has made it (stratified splits)."""
     from .recommendation import ALS, ALSModel
     metrics, subs = [], ([] if collect else None)
     if not isinstance(estimator, ALS):
@@ -131,12 +140,13 @@ def _fit_and_score(estimator, maps, evaluator, train, validation, collect: bool)
                 subs.append(model)
         return metrics, subs
     from .. import engine as _engine
-    core, built_for = None, None
+    built_for = None
     for m in maps:
         est = estimator.copy(m)
         cols = tuple(est.getOrDefault(c) for c in ("userCol", "itemCol", "ratingCol"))
-        if core is None or cols != built_for:
-            core, built_for = _engine.make_engine(*est._columns(train)), cols
+        if core is None or (built_for is not None and cols != built_for):
+            core = _engine.make_engine(*est._columns(train))
+        built_for = cols
         est._fit_core(core, checkpoints=False)
         model = ALSModel(core, dict(est._p), solver=est.getSolver())
         metrics.append(_score(evaluator, model, validation))   # before the next fit
@@ -146,6 +156,48 @@ def _fit_and_score(estimator, maps, evaluator, train, validation, collect: bool)
             subs.append(ALSModel(_engine.ALSCore.from_factors(uids, U, iids, V), dict(est._p),
                                  solver=est.getSolver()))
     return metrics, subs
+
+
+def _check_stratify(stratify):
+    if stratify not in (None, "user"):
+        raise ValueError(f"stratify must be None or \"user\", got {stratify!r}")
+    return stratify
+
+
+def _stratified_splits(estimator, maps, dataset, split_args, seed):
+    """For each kwargs of `split_args` (count / fraction / fold for ALSCore.split) one
+    (train, validation, core): the full engine is built once from the estimator's columns and
+    split on the device.  With an ALS estimator `core` is the training engine and `train` is
+    not materialised; any other estimator gets host dicts of columns for both parts."""
+    from .. import engine as _engine
+    from .recommendation import ALS
+    if isinstance(estimator, ALS):
+        ests = [estimator.copy(m) for m in maps]
+        names = {tuple(e.getOrDefault(c) for c in ("userCol", "itemCol", "ratingCol"))
+                 for e in ests}
+        if len(names) != 1:
+            raise ValueError("stratify=\"user\" needs one userCol / itemCol / ratingCol for "
+                             "every param map")
+        names, = names
+        trip = ests[0]._columns(dataset)
+    else:   # the estimator's own column params, else the names every estimator here defaults to
+        get = getattr(estimator, "getOrDefault", None)
+        names = tuple(get(c) if get is not None else d for c, d in
+                      (("userCol", "user"), ("itemCol", "item"), ("ratingCol", "rating")))
+        from .._data import check_integers, columns_of, to_float32
+        u, i, r = columns_of(dataset, names)
+        trip = check_integers(u, names[0]), check_integers(i, names[1]), to_float32(r)
+    full = _engine.ALSCore(*trip)
+    for kw in split_args:
+        core, held = full.split(seed=seed, **kw)
+        if held[0].numel() == 0:
+            raise ValueError("the stratified split left the validation side empty")
+        validation = {n: x.cpu().numpy() for n, x in zip(names, held)}
+        if isinstance(estimator, ALS):
+            yield None, validation, core
+        else:
+            kept = _datasets.core_triples(core)
+            yield {n: x.cpu().numpy() for n, x in zip(names, kept)}, validation, None
 
 
 class _Tuner:
@@ -176,6 +228,9 @@ class _Tuner:
     def getSeed(self) -> int:
         return self.seed
 
+    def getStratify(self):
+        return self.stratify
+
 
 class _TunedModel:
     def transform(self, dataset):
@@ -197,21 +252,48 @@ class TrainValidationSplit(_Tuner):
     (1 - trainRatio), every map fitted on the training part and scored on the rest."""
 
     def __init__(self, estimator, estimatorParamMaps, evaluator, trainRatio: float = 0.75,
-                 seed=None, parallelism: int = 1, collectSubModels: bool = False):
+                 seed=None, parallelism: int = 1, collectSubModels: bool = False,
+                 stratify=None, holdOut=None):
+        """stratify="user": the split is made per user on the GPU (module docstring), every
+        user giving 1 - trainRatio of their ratings to the validation part, or `holdOut`
+        ratings when that is given (holdOut=1 is leave-one-out, the protocol HR@k, NDCG@k and
+        MRR are usually reported under)."""
         if not 0.0 < float(trainRatio) < 1.0:
             raise ValueError(f"trainRatio must be in (0, 1), got {trainRatio!r}")
         self.trainRatio = float(trainRatio)
+        self.stratify = _check_stratify(stratify)
+        if holdOut is not None:
+            if stratify is None:
+                raise ValueError("holdOut needs stratify=\"user\"")
+            if isinstance(holdOut, bool) or int(holdOut) != holdOut or int(holdOut) < 1:
+                raise ValueError(f"holdOut must be an integer >= 1, got {holdOut!r}")
+            holdOut = int(holdOut)
+        self.holdOut = holdOut
         self._init_common(estimator, estimatorParamMaps, evaluator, seed, parallelism,
                           collectSubModels)
 
     def getTrainRatio(self) -> float:
         return self.trainRatio
 
+    def getHoldOut(self):
+        return self.holdOut
+
     def split(self, n: int):
         """(training rows, validation rows) of an n-row dataset: datasets.random_split."""
         return _datasets.random_split(n, (self.trainRatio, 1.0 - self.trainRatio), self.seed)
 
     def fit(self, dataset) -> TrainValidationSplitModel:
+        if self.stratify:
+            kw = (dict(count=self.holdOut) if self.holdOut is not None
+                  else dict(fraction=1.0 - self.trainRatio))
+            (train, va, core), = _stratified_splits(self.estimator, self.estimatorParamMaps,
+                                                    dataset, [kw], self.seed)
+            metrics, subs = _fit_and_score(self.estimator, self.estimatorParamMaps,
+                                           self.evaluator, train, va, self.collectSubModels,
+                                           core)
+            best = best_index(metrics, self.evaluator.isLargerBetter())
+            return TrainValidationSplitModel(
+                self.estimator.fit(dataset, self.estimatorParamMaps[best]), metrics, subs)
         tr, va = self.split(_n_rows(dataset))
         if len(tr) == 0 or len(va) == 0:
             raise ValueError("the train/validation split left one side empty")
@@ -242,12 +324,19 @@ class CrossValidator(_Tuner):
 
     def __init__(self, estimator, estimatorParamMaps, evaluator, numFolds: int = 3,
                  foldCol: str = "", seed=None, parallelism: int = 1,
-                 collectSubModels: bool = False):
+                 collectSubModels: bool = False, stratify=None):
+        """stratify="user": fold f holds, of every user, part f of numFolds parts of their
+        ratings (sizes within one of each other), made on the GPU (module docstring); it
+        cannot be combined with foldCol."""
         if isinstance(numFolds, bool) or not isinstance(numFolds, (int, np.integer)) \
                 or numFolds < 2:
             raise ValueError(f"numFolds must be >= 2, got {numFolds!r}")
         self.numFolds = int(numFolds)
         self.foldCol = str(foldCol or "")
+        self.stratify = _check_stratify(stratify)
+        if self.stratify and self.foldCol:
+            raise ValueError("foldCol and stratify cannot be combined: the folds come from one "
+                             "or the other")
         self._init_common(estimator, estimatorParamMaps, evaluator, seed, parallelism,
                           collectSubModels)
 
@@ -274,15 +363,25 @@ class CrossValidator(_Tuner):
                              f"got {int(f.min())} .. {int(f.max())}")
         return f
 
-    def fit(self, dataset) -> CrossValidatorModel:
+    def _splits(self, dataset):
+        """(train, validation, training engine or None) of every fold."""
+        if self.stratify:
+            kws = [dict(fold=(f, self.numFolds)) for f in range(self.numFolds)]
+            yield from _stratified_splits(self.estimator, self.estimatorParamMaps, dataset, kws,
+                                          self.seed)
+            return
         fold = self.folds(dataset)
-        all_metrics, subs = [], ([] if self.collectSubModels else None)
         for f in range(self.numFolds):
             va, tr = np.nonzero(fold == f)[0], np.nonzero(fold != f)[0]
             if len(tr) == 0 or len(va) == 0:
                 raise ValueError(f"fold {f} left the training or the validation side empty")
+            yield _take(dataset, tr), _take(dataset, va), None
+
+    def fit(self, dataset) -> CrossValidatorModel:
+        all_metrics, subs = [], ([] if self.collectSubModels else None)
+        for train, va, core in self._splits(dataset):
             m, s = _fit_and_score(self.estimator, self.estimatorParamMaps, self.evaluator,
-                                  _take(dataset, tr), _take(dataset, va), self.collectSubModels)
+                                  train, va, self.collectSubModels, core)
             all_metrics.append(m)
             if subs is not None:
                 subs.append(s)

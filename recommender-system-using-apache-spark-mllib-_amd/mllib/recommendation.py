@@ -484,6 +484,31 @@ class ALS:
         return MatrixFactorizationModel(core)
 
     @classmethod
+    def trainHoldout(cls, ratings, rank: int, iterations: int = 5, lambda_: float = 0.01,
+                     blocks: int = -1, nonnegative: bool = False, seed: Optional[int] = None,
+                     holdOut: int = 1, splitSeed: Optional[int] = None):
+        """train() under the leave-k-out protocol: `holdOut` ratings of every user are held
+        out (holdOut=1: leave-one-out), chosen on the GPU from (splitSeed, user, product)
+        (ALSCore.split, K20; no product leaves the training part), and the model is trained
+        on the rest.  Returns (model, held): held is the list of held-out Rating rows, users
+        ascending, a user's ratings in input order.  splitSeed None = seed.  Not a pyspark
+        method."""
+        _check(rank, iterations, lambda_, nonnegative)
+        if isinstance(holdOut, bool) or int(holdOut) != holdOut or int(holdOut) < 1:
+            raise ValueError(f"holdOut must be an integer >= 1, got {holdOut!r}")
+        u, i, r = _triples(ratings)
+        full = _engine.make_engine(u, i, r)
+        if not isinstance(full, _engine.ALSCore):
+            raise NotImplementedError("trainHoldout needs the single-GPU engine")
+        seed = _DEFAULT_SEED if seed is None else int(seed)
+        core, held = full.split(count=int(holdOut),
+                                seed=seed if splitSeed is None else int(splitSeed))
+        del full
+        core.fit(int(rank), int(iterations), float(lambda_), False, 1.0, seed=seed)
+        hu, hi, hr = (x.cpu().numpy().tolist() for x in held)
+        return MatrixFactorizationModel(core), [Rating(*t) for t in zip(hu, hi, hr)]
+
+    @classmethod
     def trainImplicit(cls, ratings, rank: int, iterations: int = 5, lambda_: float = 0.01,
                       blocks: int = -1, alpha: float = 0.01, nonnegative: bool = False,
                       seed: Optional[int] = None) -> MatrixFactorizationModel:
