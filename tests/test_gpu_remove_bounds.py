@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import guard_arena as G
+import many_rows_ref as MR
 import remove_ref as RR
 from als_mi355x import _lib
 
@@ -111,3 +112,18 @@ def test_csr_remove_plain_copy_guarded(user_side):
     nnz = len(inp["col_old"])
     bits = np.unpackbits(got[0].view(np.uint8), bitorder="little")
     assert bits[:nnz].all() and not bits[nnz:].any()
+
+
+@pytest.mark.parametrize("user_side", [True, False])
+@pytest.mark.parametrize("kind", ["every_5th", "seam_rows"])
+def test_csr_remove_seams_guarded(kind, user_side):
+    """many_rows_ref.seams: about 1100 rows, a tile that walks two batches of 256 rows with
+    long rows on both sides of the seam; one entry of every 5th row leaves, or every entry of
+    the rows on a seam."""
+    T = _lib.lib().als_csr_remove_tile()
+    old = MR.seams(T)
+    inp, want = RR.side_inputs(old, MR.delete_pairs(old, kind, T), user_side)
+    got = _both_fills(inp)
+    assert RR.row_ptr_of(got[2], want["new_of_old_row"]).tobytes() == want["csr"][0].tobytes()
+    assert got[3].tobytes() == want["csr"][1].tobytes()
+    assert got[4].tobytes() == want["csr"][2].tobytes()

@@ -11,8 +11,9 @@ import pytest
 import torch
 
 import guard_arena as G
+import many_rows_ref as MR
 from als_mi355x import _lib
-from test_gpu_split import CAP, SEED, _expected, _ref
+from test_gpu_split import CAP, SEED, WINDOWS, _expected, _ref
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -85,6 +86,28 @@ def test_split_all_guarded(shape, window, user_side, row_cap):
     for fill in (0x00, 0xFF):
         arena = G.Arena(DEV, fill)   # some 25 carves, 2 MiB of guard each
         outs.append(_run(arena, sp, row_cap))
+        bad = arena.check()
+        assert not bad, (f"fill {fill:#04x}: bytes outside a buffer were written: "
+                         f"{ {k: (v[:8], len(v)) for k, v in bad.items()} }")
+    want = _expected(sp)
+    assert sorted(outs[0]) == sorted(want)
+    for k in want:
+        assert outs[0][k].tobytes() == outs[1][k].tobytes(), f"{k} depends on the arena's fill"
+        assert outs[0][k].dtype == want[k].dtype and outs[0][k].tobytes() == want[k].tobytes(), k
+
+
+@pytest.mark.parametrize("window", ["fold1of3", "last"])
+def test_split_many_listed_guarded(window):
+    """many_rows_ref.many_listed at row_cap = 1: every one of the 2 * 2048 + 37 selecting rows
+    is listed, so the list fills its part of the scratch and a workgroup of the long-row
+    kernel takes two or three rows."""
+    sp = MR.FastSplit(seed=SEED, keep_items=True, user_side=True, **MR.many_listed())
+    w = WINDOWS[window]
+    sp.set_windows(w.get("mode"), w.get("value"), w.get("min_keep", 1), w.get("win"))
+    outs = []
+    for fill in (0x00, 0xFF):
+        arena = G.Arena(DEV, fill)
+        outs.append(_run(arena, sp, 1))
         bad = arena.check()
         assert not bad, (f"fill {fill:#04x}: bytes outside a buffer were written: "
                          f"{ {k: (v[:8], len(v)) for k, v in bad.items()} }")

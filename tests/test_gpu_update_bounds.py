@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import guard_arena as G
+import many_rows_ref as MR
 import update_ref as UR
 from als_mi355x import _lib
 
@@ -108,3 +109,28 @@ def test_csr_merge_empty_rows_and_empty_sides_guarded():
     assert arena.check() == {}
     for a, r in zip(got, add):
         assert a.tobytes() == r.tobytes()
+
+
+@pytest.mark.parametrize("user_side", [True, False])
+@pytest.mark.parametrize("kind", ["b_new_rows", "c_new_cols"])
+def test_csr_merge_seams_guarded(kind, user_side):
+    """many_rows_ref.seams: about 1100 rows, a tile that walks two batches of 256 rows with
+    long rows on both sides of the seam; new rows in every gap (a row map of 1100 entries, the
+    row pointer over several workgroups) or new columns."""
+    T = _lib.lib().als_csr_merge_tile()
+    old = MR.seams(T)
+    inp, want = UR.side_inputs(old, MR.batch(old, kind), user_side)
+    assert (inp["new_of_old_row"] is None) == ((kind == "c_new_cols") == user_side)
+    outs = []
+    for fill in (0x00, 0xFF):
+        arena = G.Arena(DEV, fill, capacity=48 << 20)
+        outs.append(_run(arena, inp))
+        bad = arena.check()
+        assert not bad, (f"fill {fill:#04x}: bytes outside a buffer were written: "
+                         f"{ {k: (v[:8], len(v)) for k, v in bad.items()} }")
+    ref = UR.merge(inp["row_ptr_old"], inp["col_old"], inp["val_old"], inp["new_of_old_row"],
+                   inp["new_of_old_col"], inp["row_ptr_add"], inp["col_add"], inp["val_add"])
+    for a, b, r, w in zip(outs[0], outs[1], ref, want):
+        assert a.tobytes() == b.tobytes(), "the output depends on the arena's fill"
+        assert a.dtype == r.dtype and a.tobytes() == r.tobytes()
+        assert a.tobytes() == w.tobytes()
