@@ -87,13 +87,26 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {
   return __builtin_bit_cast(double, iv);
 }
 
-__device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
+// Wave shuffles of a 64-bit value (int64_t, uint64_t, double): two 32-bit shuffles of its halves.
+template <class T>
+__device__ __forceinline__ T shfl_xor_64(T v, int mask) {
+  static_assert(sizeof(T) == 8, "shfl_xor_64: a 64-bit type");
   int2 iv = __builtin_bit_cast(int2, v);
   iv.x = __shfl_xor(iv.x, mask);
   iv.y = __shfl_xor(iv.y, mask);
-  return __builtin_bit_cast(double, iv);
+  return __builtin_bit_cast(T, iv);
 }
 
+template <class T>
+__device__ __forceinline__ T shfl_up_64(T v, int delta) {
+  static_assert(sizeof(T) == 8, "shfl_up_64: a 64-bit type");
+  int2 iv = __builtin_bit_cast(int2, v);
+  iv.x = __shfl_up(iv.x, delta);
+  iv.y = __shfl_up(iv.y, delta);
+  return __builtin_bit_cast(T, iv);
+}
+
+__device__ __forceinline__ double shfl_xor_f64(double v, int mask) { return shfl_xor_64(v, mask); }
 
 // <U[umap[uid]], V[imap[iid]]> in fp64 over the fp32 factors, for the 16-lane group of the
 // calling lane (K4 predict / RMSE, K8 regression moments): each lane takes one float4 of

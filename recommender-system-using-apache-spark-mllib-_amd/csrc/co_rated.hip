@@ -60,10 +60,8 @@ __global__ __launch_bounds__(64) void cr_plan_kernel(const int64_t* __restrict__
   int64_t incl = (len + task - 1) / task;
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
-    int2 iv = __builtin_bit_cast(int2, incl);
-    iv.x = __shfl_up(iv.x, o);
-    iv.y = __shfl_up(iv.y, o);
-    if (lane >= o) incl += __builtin_bit_cast(int64_t, iv);
+    const int64_t up = shfl_up_64(incl, o);
+    if (lane >= o) incl += up;
   }
   if (lane < nq) task_off[lane + 1] = incl;
   if (lane == 0) task_off[0] = 0;

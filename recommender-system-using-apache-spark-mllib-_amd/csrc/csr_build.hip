@@ -27,19 +27,6 @@ void set_error(const char* fmt, ...) {
 // ----------------------------------------------------------------------------
 // Block-wide helpers (256 threads = 4 wavefronts of 64)
 // ----------------------------------------------------------------------------
-__device__ __forceinline__ int64_t shfl_up_i64(int64_t v, int d) {
-  int2 iv = __builtin_bit_cast(int2, v);
-  iv.x = __shfl_up(iv.x, d);
-  iv.y = __shfl_up(iv.y, d);
-  return __builtin_bit_cast(int64_t, iv);
-}
-__device__ __forceinline__ int64_t shfl_xor_i64(int64_t v, int d) {
-  int2 iv = __builtin_bit_cast(int2, v);
-  iv.x = __shfl_xor(iv.x, d);
-  iv.y = __shfl_xor(iv.y, d);
-  return __builtin_bit_cast(int64_t, iv);
-}
-
 // Exclusive scan of one int64 per thread over a 256-thread block; *total gets the block sum.
 __device__ __forceinline__ int64_t block_exclusive_scan_256(int64_t v, int64_t* total) {
   __shared__ int64_t wsum[4];
@@ -47,7 +34,7 @@ __device__ __forceinline__ int64_t block_exclusive_scan_256(int64_t v, int64_t* 
   int64_t inc = v;
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
-    int64_t o = shfl_up_i64(inc, d);
+    int64_t o = shfl_up_64(inc, d);
     if (lane >= d) inc += o;
   }
   if (lane == 63) wsum[w] = inc;
@@ -67,7 +54,7 @@ __device__ __forceinline__ int64_t block_exclusive_scan_256(int64_t v, int64_t* 
 __device__ __forceinline__ int64_t block_reduce_sum_256(int64_t v) {
   __shared__ int64_t wsum[4];
 #pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += shfl_xor_i64(v, d);
+  for (int d = 32; d >= 1; d >>= 1) v += shfl_xor_64(v, d);
   if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
   __syncthreads();
   int64_t t = wsum[0] + wsum[1] + wsum[2] + wsum[3];

@@ -13,12 +13,9 @@
 // so the copy kernel reads nothing but O and A to place an entry.  One streaming pass:
 // integer and copy work only, no atomics, every output word written exactly once.
 #include "als_common.h"
+#include "csr_tile_walk.h"
 
 namespace als {
-
-constexpr int kMergeThreads = 256;
-constexpr int kMergeItems = 8;
-constexpr int kMergeTile = kMergeThreads * kMergeItems;  // output entries per workgroup
 
 // O[r] = P[j(r)] + A[r], j(r) = #{old rows whose new row is < r}: a lower bound in the
 // strictly increasing new_of_old_row (NULL = identity: j(r) = min(r, n_old)).
@@ -42,80 +39,58 @@ __global__ __launch_bounds__(256) void merge_row_ptr_kernel(
   row_ptr_out[r] = row_ptr_old[j] + row_ptr_add[r];
 }
 
-// One tile of kMergeTile output entries per workgroup, whichever rows they fall in.  The
-// tile's first row comes from one binary search in O; from there the rows are walked 256
-// at a time: their ends and the two source offsets go to LDS, and every entry finds its
-// row among them (8 steps in LDS).  Thread t copies entries t, t + 256, ...: along a run
-// of one source the loads and the stores of a wavefront are consecutive words.
-__global__ __launch_bounds__(kMergeThreads) void merge_copy_kernel(
+// One tile of kTile output entries per workgroup, walked by tile_row_walk (csr_tile_walk.h)
+// over O: beside a row's end the two source offsets go to LDS, and an entry needs nothing else
+// to find its source.
+__global__ __launch_bounds__(kTileThreads) void merge_copy_kernel(
     const int32_t* __restrict__ col_old, const uint32_t* __restrict__ val_old, int64_t nnz_old,
     const int32_t* __restrict__ new_of_old_col, int32_t n_cols_old,
     const int64_t* __restrict__ row_ptr_add, const int32_t* __restrict__ col_add,
     const uint32_t* __restrict__ val_add, int64_t nnz_add, int32_t n_new,
     const int64_t* __restrict__ row_ptr_out, int32_t* __restrict__ col_out,
     uint32_t* __restrict__ val_out) {
-  __shared__ int64_t s_end[kMergeThreads];   // O[r + 1]
-  __shared__ int64_t s_add0[kMergeThreads];  // A[r]
-  __shared__ int64_t s_old1[kMergeThreads];  // O[r + 1] - A[r + 1] = P[j(r + 1)]
+  __shared__ int64_t s_end[kTileThreads];   // O[r + 1]
+  __shared__ int64_t s_add0[kTileThreads];  // A[r]
+  __shared__ int64_t s_old1[kTileThreads];  // O[r + 1] - A[r + 1] = P[j(r + 1)]
   const int64_t nnz_out = nnz_old + nnz_add;
-  const int64_t p0 = (int64_t)blockIdx.x * kMergeTile;
-  const int64_t p1 = p0 + kMergeTile < nnz_out ? p0 + kMergeTile : nnz_out;
+  const int64_t p0 = (int64_t)blockIdx.x * kTile;
+  const int64_t p1 = p0 + kTile < nnz_out ? p0 + kTile : nnz_out;
   const int t = threadIdx.x;
-
-  // the last row r with O[r] <= p0 (O[n_new] = nnz_out > p0, so r < n_new)
-  int32_t lo = 0, hi = n_new;
-  while (lo < hi) {
-    const int32_t mid = lo + ((hi - lo + 1) >> 1);
-    if (row_ptr_out[mid] <= p0) lo = mid; else hi = mid - 1;
-  }
-  int64_t row0 = lo;
-  int64_t done = p0;  // entries below `done` are written
-  while (done < p1) {
-    const int64_t r = row0 + t;
-    int64_t end = nnz_out, add0 = nnz_add, old1 = nnz_old;  // past the last row: no entries
-    if (r < n_new) {
-      end = row_ptr_out[r + 1];
-      add0 = row_ptr_add[r];
-      old1 = end - row_ptr_add[r + 1];
-    }
-    s_end[t] = end;
-    s_add0[t] = add0;
-    s_old1[t] = old1;
-    __syncthreads();
-    const int64_t batch_end = s_end[kMergeThreads - 1];
-    const int64_t stop = batch_end < p1 ? batch_end : p1;
-#pragma unroll
-    for (int i = 0; i < kMergeItems; ++i) {
-      const int64_t q = p0 + i * kMergeThreads + t;
-      if (q < done || q >= stop) continue;
-      int a = 0, b = kMergeThreads - 1;  // first row of the batch with end > q
-      while (a < b) {
-        const int mid = (a + b) >> 1;
-        if (s_end[mid] > q) b = mid; else a = mid + 1;
-      }
-      const int64_t src_old = q - s_add0[a], o1 = s_old1[a];
-      int32_t c = -1;
-      uint32_t v = 0;
-      if (src_old < o1) {
-        if (src_old >= 0 && src_old < nnz_old) {
-          c = col_old[src_old];
-          v = val_old[src_old];
-          if (new_of_old_col != nullptr) c = (c >= 0 && c < n_cols_old) ? new_of_old_col[c] : -1;
+  // O[n_new] = nnz_out > p0, so the tile's first row is below n_new
+  tile_row_walk(
+      p0, p1, csr_row_at(row_ptr_out, n_new, p0), s_end,
+      [&](int64_t r) {
+        int64_t end = nnz_out, add0 = nnz_add, old1 = nnz_old;  // past the last row: no entries
+        if (r < n_new) {
+          end = row_ptr_out[r + 1];
+          add0 = row_ptr_add[r];
+          old1 = end - row_ptr_add[r + 1];
         }
-      } else {
-        const int64_t src_add = q - o1;
-        if (src_add >= 0 && src_add < nnz_add) {
-          c = col_add[src_add];
-          v = val_add[src_add];
+        s_end[t] = end;
+        s_add0[t] = add0;
+        s_old1[t] = old1;
+      },
+      [&](int, int64_t q, int a, int64_t) {
+        const int64_t src_old = q - s_add0[a], o1 = s_old1[a];
+        int32_t c = -1;
+        uint32_t v = 0;
+        if (src_old < o1) {
+          if (src_old >= 0 && src_old < nnz_old) {
+            c = col_old[src_old];
+            v = val_old[src_old];
+            if (new_of_old_col != nullptr)
+              c = (c >= 0 && c < n_cols_old) ? new_of_old_col[c] : -1;
+          }
+        } else {
+          const int64_t src_add = q - o1;
+          if (src_add >= 0 && src_add < nnz_add) {
+            c = col_add[src_add];
+            v = val_add[src_add];
+          }
         }
-      }
-      col_out[q] = c;
-      val_out[q] = v;
-    }
-    done = stop;
-    row0 += kMergeThreads;
-    __syncthreads();  // the next batch overwrites the LDS rows
-  }
+        col_out[q] = c;
+        val_out[q] = v;
+      });
 }
 
 }  // namespace als
@@ -124,7 +99,7 @@ using namespace als;
 
 extern "C" {
 
-int32_t als_csr_merge_tile(void) { return kMergeTile; }
+int32_t als_csr_merge_tile(void) { return kTile; }
 
 int als_csr_merge(const int64_t* row_ptr_old, const int32_t* col_old, const float* val_old,
                   int64_t nnz_old, int32_t n_old, int32_t n_cols_old,
@@ -154,8 +129,7 @@ int als_csr_merge(const int64_t* row_ptr_old, const int32_t* col_old, const floa
       row_ptr_old, n_old, new_of_old_row, row_ptr_add, n_new, row_ptr_out);
   ALS_LAUNCH_CHECK();
   if (nnz_out > 0) {
-    const int64_t tiles = (nnz_out + kMergeTile - 1) / kMergeTile;
-    merge_copy_kernel<<<(unsigned)tiles, kMergeThreads, 0, st>>>(
+    merge_copy_kernel<<<(unsigned)csr_tiles(nnz_out), kTileThreads, 0, st>>>(
         col_old, reinterpret_cast<const uint32_t*>(val_old), nnz_old, new_of_old_col, n_cols_old,
         row_ptr_add, col_add, reinterpret_cast<const uint32_t*>(val_add), nnz_add, n_new,
         row_ptr_out, col_out, reinterpret_cast<uint32_t*>(val_out));

@@ -12,7 +12,9 @@
 //            entries before row_ptr_old[r] = tile_off of the tile + popcounts below it.
 //   compact  each kept entry goes to tile_off[tile] + its rank among the tile's kept entries,
 //            its column through the other side's old-to-new row map, its value as bits.
-// Work is split over stored ENTRIES, kRemoveTile per workgroup whichever rows they fall in.
+// Work is split over stored ENTRIES, kTile per workgroup whichever rows they fall in: the tile
+// and its row walk are csr_tile_walk.h's (shared with K17 and K20), the keep-bits tail, the
+// scan and the row pass csr_compact.h's (shared with K20).
 // Integer and copy work only; the one atomic (the optional per-pair hit count) is an integer
 // add, so two calls give identical bytes.
 #include "als_common.h"
@@ -20,125 +22,85 @@
 
 namespace als {
 
-// One tile of stored entries per workgroup.  Rows are walked as in K17's copy kernel: the
-// tile's first row from one binary search in row_ptr_old, then 256 rows at a time with their
-// ends and delete ranges in LDS.  Thread t owns entries t, t + 256, ...; its eight keep flags
-// stay in a register until every row batch is done, then a ballot per item makes the words.
-__global__ __launch_bounds__(kRemoveThreads) void remove_mark_kernel(
+// One tile of stored entries per workgroup, walked by tile_row_walk (csr_tile_walk.h) over
+// row_ptr_old with the rows' delete ranges in LDS beside their ends.  Thread t owns entries t,
+// t + 256, ...; its eight keep flags stay in a register until every row batch is done, then
+// tile_store_keep (csr_compact.h) makes the words.
+__global__ __launch_bounds__(kTileThreads) void remove_mark_kernel(
     const int64_t* __restrict__ row_ptr_old, const int32_t* __restrict__ col_old,
     int64_t nnz_old, int32_t n_old, const int64_t* __restrict__ row_ptr_del,
     const int32_t* __restrict__ col_del, int64_t nnz_del, uint64_t* __restrict__ keep_bits,
     int32_t* __restrict__ tile_cnt, int32_t* __restrict__ del_hits) {
-  __shared__ int64_t s_end[kRemoveThreads];   // P[r + 1]
-  __shared__ int64_t s_del0[kRemoveThreads];  // D[r]
-  __shared__ int64_t s_del1[kRemoveThreads];  // D[r + 1]
-  __shared__ int32_t s_cnt[kRemoveWaves];
-  const int64_t p0 = (int64_t)blockIdx.x * kRemoveTile;
-  const int64_t p1 = p0 + kRemoveTile < nnz_old ? p0 + kRemoveTile : nnz_old;
+  __shared__ int64_t s_end[kTileThreads];   // P[r + 1]
+  __shared__ int64_t s_del0[kTileThreads];  // D[r]
+  __shared__ int64_t s_del1[kTileThreads];  // D[r + 1]
+  __shared__ int32_t s_cnt[kTileWaves];
+  const int64_t p0 = (int64_t)blockIdx.x * kTile;
+  const int64_t p1 = p0 + kTile < nnz_old ? p0 + kTile : nnz_old;
   const int t = threadIdx.x;
-
-  // the last row r with P[r] <= p0 (P[n_old] = nnz_old > p0, so r < n_old)
-  int32_t lo = 0, hi = n_old;
-  while (lo < hi) {
-    const int32_t mid = lo + ((hi - lo + 1) >> 1);
-    if (row_ptr_old[mid] <= p0) lo = mid; else hi = mid - 1;
-  }
-  int64_t row0 = lo;
-  int64_t done = p0;  // entries below `done` are marked
   uint32_t keep = 0;  // bit i: entry p0 + i * 256 + t stays
-  while (done < p1) {
-    const int64_t r = row0 + t;
-    int64_t end = nnz_old, d0 = 0, d1 = 0;  // past the last row: no entries, no deletes
-    if (r < n_old) {
-      end = row_ptr_old[r + 1];
-      if (row_ptr_del != nullptr) {
-        d0 = row_ptr_del[r];
-        d1 = row_ptr_del[r + 1];
-      }
-    }
-    s_end[t] = end;
-    s_del0[t] = d0;
-    s_del1[t] = d1;
-    __syncthreads();
-    const int64_t batch_end = s_end[kRemoveThreads - 1];
-    const int64_t stop = batch_end < p1 ? batch_end : p1;
-#pragma unroll
-    for (int i = 0; i < kRemoveItems; ++i) {
-      const int64_t q = p0 + i * kRemoveThreads + t;
-      if (q < done || q >= stop) continue;
-      int a = 0, b = kRemoveThreads - 1;  // first row of the batch with end > q
-      while (a < b) {
-        const int mid = (a + b) >> 1;
-        if (s_end[mid] > q) b = mid; else a = mid + 1;
-      }
-      int64_t dl = s_del0[a], dh = s_del1[a];
-      bool stays = true;
-      if (dl < dh) {  // the row has a delete list: is this entry's column in it?
-        if (dl < 0) dl = 0;
-        if (dh > nnz_del) dh = nnz_del;
-        const int64_t top = dh;
-        const int32_t c = col_old[q];
-        while (dl < dh) {  // first listed column >= c
-          const int64_t mid = dl + ((dh - dl) >> 1);
-          if (col_del[mid] < c) dl = mid + 1; else dh = mid;
+  // P[n_old] = nnz_old > p0, so the tile's first row is below n_old
+  tile_row_walk(
+      p0, p1, csr_row_at(row_ptr_old, n_old, p0), s_end,
+      [&](int64_t r) {
+        int64_t end = nnz_old, d0 = 0, d1 = 0;  // past the last row: no entries, no deletes
+        if (r < n_old) {
+          end = row_ptr_old[r + 1];
+          if (row_ptr_del != nullptr) {
+            d0 = row_ptr_del[r];
+            d1 = row_ptr_del[r + 1];
+          }
         }
-        if (dl < top && col_del[dl] == c) {
-          stays = false;
-          if (del_hits != nullptr) atomicAdd(del_hits + dl, 1);
+        s_end[t] = end;
+        s_del0[t] = d0;
+        s_del1[t] = d1;
+      },
+      [&](int i, int64_t q, int a, int64_t) {
+        int64_t dl = s_del0[a], dh = s_del1[a];
+        bool stays = true;
+        if (dl < dh) {  // the row has a delete list: is this entry's column in it?
+          if (dl < 0) dl = 0;
+          if (dh > nnz_del) dh = nnz_del;
+          const int64_t top = dh;
+          const int32_t c = col_old[q];
+          while (dl < dh) {  // first listed column >= c
+            const int64_t mid = dl + ((dh - dl) >> 1);
+            if (col_del[mid] < c) dl = mid + 1; else dh = mid;
+          }
+          if (dl < top && col_del[dl] == c) {
+            stays = false;
+            if (del_hits != nullptr) atomicAdd(del_hits + dl, 1);
+          }
         }
-      }
-      if (stays) keep |= 1u << i;
-    }
-    if (stop > done) done = stop;
-    row0 += kRemoveThreads;
-    __syncthreads();  // the next batch overwrites the LDS rows
-  }
-
-  // entries at or past nnz_old never set a flag: the tail bits of the last word are 0
-  const int wave = t >> 6, lane = t & 63;
-  const int64_t n_words = (nnz_old + 63) >> 6;
-  int32_t cnt = 0;
-#pragma unroll
-  for (int i = 0; i < kRemoveItems; ++i) {
-    const uint64_t word = __ballot((keep >> i) & 1u);
-    const int64_t w = (p0 >> 6) + i * kRemoveWaves + wave;
-    if (lane == 0 && w < n_words) keep_bits[w] = word;
-    cnt += __popcll(word);
-  }
-  if (lane == 0) s_cnt[wave] = cnt;
-  __syncthreads();
-  if (t == 0) {
-    int32_t sum = 0;
-#pragma unroll
-    for (int w = 0; w < kRemoveWaves; ++w) sum += s_cnt[w];
-    tile_cnt[blockIdx.x] = sum;
-  }
+        if (stays) keep |= 1u << i;
+      });
+  tile_store_keep(keep, p0, nnz_old, keep_bits, tile_cnt, s_cnt);
 }
 
 // One tile per workgroup.  The first wave loads the tile's words and scans their popcounts;
 // an entry's place is tile_off[tile] + kept entries of the words before its own + kept bits
 // below it in its word.  Loads of a wavefront are consecutive words, and so are its stores.
-__global__ __launch_bounds__(kRemoveThreads) void remove_compact_kernel(
+__global__ __launch_bounds__(kTileThreads) void remove_compact_kernel(
     const int32_t* __restrict__ col_old, const uint32_t* __restrict__ val_old, int64_t nnz_old,
     const uint64_t* __restrict__ keep_bits, const int64_t* __restrict__ tile_off,
     const int32_t* __restrict__ new_of_old_col, int32_t n_cols_old,
     int32_t* __restrict__ col_out, uint32_t* __restrict__ val_out, int64_t nnz_out) {
-  __shared__ uint64_t s_word[kRemoveWords];
-  __shared__ int32_t s_before[kRemoveWords];
-  const int64_t p0 = (int64_t)blockIdx.x * kRemoveTile;
+  __shared__ uint64_t s_word[kTileWords];
+  __shared__ int32_t s_before[kTileWords];
+  const int64_t p0 = (int64_t)blockIdx.x * kTile;
   const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
   const int64_t n_words = (nnz_old + 63) >> 6;
   if (wave == 0) {
     const int64_t w = (p0 >> 6) + lane;
-    const uint64_t word = (lane < kRemoveWords && w < n_words) ? keep_bits[w] : 0;
+    const uint64_t word = (lane < kTileWords && w < n_words) ? keep_bits[w] : 0;
     const int32_t c = __popcll(word);
     int32_t incl = c;
 #pragma unroll
-    for (int d = 1; d < kRemoveWords; d <<= 1) {
+    for (int d = 1; d < kTileWords; d <<= 1) {
       const int32_t up = __shfl_up(incl, d);
       if (lane >= d) incl += up;
     }
-    if (lane < kRemoveWords) {
+    if (lane < kTileWords) {
       s_word[lane] = word;
       s_before[lane] = incl - c;
     }
@@ -146,9 +108,9 @@ __global__ __launch_bounds__(kRemoveThreads) void remove_compact_kernel(
   __syncthreads();
   const int64_t out0 = tile_off[blockIdx.x];
 #pragma unroll
-  for (int i = 0; i < kRemoveItems; ++i) {
-    const int64_t q = p0 + i * kRemoveThreads + t;
-    const int wi = i * kRemoveWaves + wave;
+  for (int i = 0; i < kTileItems; ++i) {
+    const int64_t q = p0 + i * kTileThreads + t;
+    const int wi = i * kTileWaves + wave;
     const uint64_t word = s_word[wi];
     if (q >= nnz_old || !((word >> lane) & 1)) continue;
     const int64_t dst = out0 + s_before[wi] + __popcll(word & ((uint64_t(1) << lane) - 1));
@@ -166,12 +128,12 @@ using namespace als;
 
 extern "C" {
 
-int32_t als_csr_remove_tile(void) { return kRemoveTile; }
+int32_t als_csr_remove_tile(void) { return kTile; }
 
 size_t als_csr_remove_scratch_bytes(int64_t nnz_old, int32_t n_old) {
   (void)n_old;  // the row pass needs no scratch; kept in the signature for a later layout
   if (nnz_old < 0) return 0;
-  const int64_t tiles = remove_tiles(nnz_old);
+  const int64_t tiles = csr_tiles(nnz_old);
   return align_up((size_t)(tiles > 0 ? tiles : 1) * sizeof(int32_t));
 }
 
@@ -195,23 +157,18 @@ int als_csr_remove_mark(const int64_t* row_ptr_old, const int32_t* col_old, int6
               "als_csr_remove_mark: scratch of %zu bytes, %zu needed", scratch_bytes,
               als_csr_remove_scratch_bytes(nnz_old, n_old));
   hipStream_t st = as_stream(stream);
-  const int64_t tiles = remove_tiles(nnz_old);
+  const int64_t tiles = csr_tiles(nnz_old);
   int32_t* tile_cnt = static_cast<int32_t*>(scratch);
   if (nnz_del == 0) row_ptr_del = nullptr;  // a plain copy: every bit set
   if (del_hits != nullptr && nnz_del > 0)
     ALS_HIP(hipMemsetAsync(del_hits, 0, (size_t)nnz_del * sizeof(int32_t), st));
   if (tiles > 0) {
-    remove_mark_kernel<<<(unsigned)tiles, kRemoveThreads, 0, st>>>(
+    remove_mark_kernel<<<(unsigned)tiles, kTileThreads, 0, st>>>(
         row_ptr_old, col_old, nnz_old, n_old, row_ptr_del, col_del, nnz_del, keep_bits, tile_cnt,
         del_hits);
     ALS_LAUNCH_CHECK();
   }
-  remove_scan_kernel<<<1, kScanThreads, 0, st>>>(tile_cnt, tiles, tile_off);
-  ALS_LAUNCH_CHECK();
-  remove_row_ptr_kernel<<<(unsigned)(((int64_t)n_old + 256) / 256), 256, 0, st>>>(
-      row_ptr_old, n_old, nnz_old, keep_bits, tile_off, row_ptr_kept);
-  ALS_LAUNCH_CHECK();
-  return ALS_OK;
+  return keep_finish(row_ptr_old, n_old, nnz_old, keep_bits, tile_cnt, tile_off, row_ptr_kept, st);
 }
 
 int als_csr_remove_compact(const int32_t* col_old, const float* val_old, int64_t nnz_old,
@@ -231,7 +188,7 @@ int als_csr_remove_compact(const int32_t* col_old, const float* val_old, int64_t
   ALS_REQUIRE(nnz_out == 0 || (col_out && val_out), ALS_EINVAL,
               "als_csr_remove_compact: null col_out / val_out with nnz_out > 0");
   if (nnz_out == 0) return ALS_OK;
-  remove_compact_kernel<<<(unsigned)remove_tiles(nnz_old), kRemoveThreads, 0,
+  remove_compact_kernel<<<(unsigned)csr_tiles(nnz_old), kTileThreads, 0,
                           as_stream(stream)>>>(
       col_old, reinterpret_cast<const uint32_t*>(val_old), nnz_old, keep_bits, tile_off,
       new_of_old_col, n_cols_old, col_out, reinterpret_cast<uint32_t*>(val_out), nnz_out);

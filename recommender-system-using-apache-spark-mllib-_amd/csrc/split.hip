@@ -21,14 +21,16 @@
 //               no result) and a workgroup per listed row selects by radix on the key's bytes,
 //               most significant first, both ranks at once in two LDS histograms, then resolves
 //               ties on (key, column) exactly.  No limit on the row length.
-//   mark        K18's tile over the stored entries of either side: the entry's row from the
-//               row walk, its key, its selecting-side row's two thresholds and the anchor; one
-//               ballot per 64 entries.  keep_bits, tile_off and row_ptr_kept are K18's
-//               (csr_compact.h finishes both), so als_csr_remove_compact reads them unchanged.
+//   mark        the tile of csr_tile_walk.h over the stored entries of either side: the entry's
+//               row from tile_row_walk, its key, its selecting-side row's two thresholds and
+//               the anchor; one ballot per 64 entries.  keep_bits, tile_off and row_ptr_kept
+//               are K18's (csr_compact.h finishes both), so als_csr_remove_compact reads them
+//               unchanged.
 // Integer work only.  The atomics are integer adds and minima on LDS words and one integer add
 // on a list counter the call zeroes itself: two calls give identical bytes.
 #include "als_common.h"
 #include "csr_compact.h"
+#include "csr_tile_walk.h"
 
 namespace als {
 
@@ -68,19 +70,12 @@ __device__ __forceinline__ uint64_t split_key(const SplitSide& s, int32_t row, i
   return z ^ (z >> 31);
 }
 
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int mask) {
-  int2 iv = __builtin_bit_cast(int2, v);
-  iv.x = __shfl_xor(iv.x, mask);
-  iv.y = __shfl_xor(iv.y, mask);
-  return __builtin_bit_cast(uint64_t, iv);
-}
-
 // the smallest composite of the wavefront, in every lane
 __device__ __forceinline__ Comp comp_wave_min(Comp a) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) {
     Comp b;
-    b.key = shfl_xor_u64(a.key, m);
+    b.key = shfl_xor_64(a.key, m);
     b.col = __shfl_xor(a.col, m);
     if (comp_less(b, a)) a = b;
   }
@@ -99,12 +94,7 @@ __device__ __forceinline__ void split_bounds(const SplitSide& s, int64_t row, in
 
 // the last row r in [0, n_rows) with row_ptr[r] <= p (n_rows >= 1)
 __device__ __forceinline__ int32_t split_row_at(const SplitSide& s, int64_t p) {
-  int32_t lo = 0, hi = s.n_rows - 1;
-  while (lo < hi) {
-    const int32_t mid = lo + ((hi - lo + 1) >> 1);
-    if (s.row_ptr[mid] <= p) lo = mid; else hi = mid - 1;
-  }
-  return lo;
+  return csr_row_at(s.row_ptr, s.n_rows - 1, p);
 }
 
 __device__ __forceinline__ bool split_eligible(const int32_t* __restrict__ anchor, int32_t row,
@@ -415,74 +405,40 @@ __global__ __launch_bounds__(256) void split_thr_long_kernel(
 
 // ---- mark ----
 
-// K18's mark kernel with the window predicate in place of the delete list.  selecting: the
-// thresholds belong to this side's rows and the anchors to its columns; else the other way.
-__global__ __launch_bounds__(kRemoveThreads) void split_mark_kernel(
+// The tile and row walk of csr_tile_walk.h and the keep-bits tail of csr_compact.h, as in K18's
+// mark kernel, with the window predicate per entry and nothing but the row's end in LDS.
+// selecting: the thresholds belong to this side's rows and the anchors to its columns; else
+// the other way.
+__global__ __launch_bounds__(kTileThreads) void split_mark_kernel(
     SplitSide s, int selecting, const uint64_t* __restrict__ lo_key,
     const int32_t* __restrict__ lo_col, const uint64_t* __restrict__ hi_key,
     const int32_t* __restrict__ hi_col, const int32_t* __restrict__ anchor,
     uint64_t* __restrict__ keep_bits, int32_t* __restrict__ tile_cnt) {
-  __shared__ int64_t s_end[kRemoveThreads];  // P[r + 1]
-  __shared__ int32_t s_cnt[kRemoveWaves];
-  const int64_t p0 = (int64_t)blockIdx.x * kRemoveTile;
-  const int64_t p1 = p0 + kRemoveTile < s.nnz ? p0 + kRemoveTile : s.nnz;
-  const int t = threadIdx.x;
-  int64_t row0 = split_row_at(s, p0);
-  int64_t done = p0;  // entries below `done` are marked
+  __shared__ int64_t s_end[kTileThreads];  // P[r + 1]
+  __shared__ int32_t s_cnt[kTileWaves];
+  const int64_t p0 = (int64_t)blockIdx.x * kTile;
+  const int64_t p1 = p0 + kTile < s.nnz ? p0 + kTile : s.nnz;
   uint32_t keep = 0;  // bit i: entry p0 + i * 256 + t stays
-  while (done < p1) {
-    const int64_t r = row0 + t;
-    s_end[t] = r < s.n_rows ? s.row_ptr[r + 1] : s.nnz;  // past the last row: no entries
-    __syncthreads();
-    const int64_t batch_end = s_end[kRemoveThreads - 1];
-    const int64_t stop = batch_end < p1 ? batch_end : p1;
-#pragma unroll
-    for (int i = 0; i < kRemoveItems; ++i) {
-      const int64_t q = p0 + i * kRemoveThreads + t;
-      if (q < done || q >= stop) continue;
-      int a = 0, b = kRemoveThreads - 1;  // first row of the batch with end > q
-      while (a < b) {
-        const int mid = (a + b) >> 1;
-        if (s_end[mid] > q) b = mid; else a = mid + 1;
-      }
-      const int64_t row = row0 + a;
-      const int32_t c = s.col[q];
-      bool stays = true;
-      if (row < s.n_rows && c >= 0 && c < s.n_cols) {
-        const int32_t sel = selecting ? (int32_t)row : c;    // row of the selecting side
-        const int32_t oth = selecting ? c : (int32_t)row;    // row of the other side
-        if (anchor == nullptr || anchor[oth] != sel) {
-          const Comp x{split_key(s, (int32_t)row, c), oth};
-          const Comp lo{lo_key[sel], lo_col[sel]}, hi{hi_key[sel], hi_col[sel]};
-          stays = comp_less(x, lo) || !comp_less(x, hi);
+  tile_row_walk(
+      p0, p1, split_row_at(s, p0), s_end,
+      [&](int64_t r) {  // past the last row: no entries
+        s_end[threadIdx.x] = r < s.n_rows ? s.row_ptr[r + 1] : s.nnz;
+      },
+      [&](int i, int64_t q, int, int64_t row) {
+        const int32_t c = s.col[q];
+        bool stays = true;
+        if (row < s.n_rows && c >= 0 && c < s.n_cols) {
+          const int32_t sel = selecting ? (int32_t)row : c;    // row of the selecting side
+          const int32_t oth = selecting ? c : (int32_t)row;    // row of the other side
+          if (anchor == nullptr || anchor[oth] != sel) {
+            const Comp x{split_key(s, (int32_t)row, c), oth};
+            const Comp lo{lo_key[sel], lo_col[sel]}, hi{hi_key[sel], hi_col[sel]};
+            stays = comp_less(x, lo) || !comp_less(x, hi);
+          }
         }
-      }
-      if (stays) keep |= 1u << i;
-    }
-    if (stop > done) done = stop;
-    row0 += kRemoveThreads;
-    __syncthreads();  // the next batch overwrites the LDS rows
-  }
-
-  // entries at or past nnz never set a flag: the tail bits of the last word are 0
-  const int wave = t >> 6, lane = t & 63;
-  const int64_t n_words = (s.nnz + 63) >> 6;
-  int32_t cnt = 0;
-#pragma unroll
-  for (int i = 0; i < kRemoveItems; ++i) {
-    const uint64_t word = __ballot((keep >> i) & 1u);
-    const int64_t w = (p0 >> 6) + i * kRemoveWaves + wave;
-    if (lane == 0 && w < n_words) keep_bits[w] = word;
-    cnt += __popcll(word);
-  }
-  if (lane == 0) s_cnt[wave] = cnt;
-  __syncthreads();
-  if (t == 0) {
-    int32_t sum = 0;
-#pragma unroll
-    for (int w = 0; w < kRemoveWaves; ++w) sum += s_cnt[w];
-    tile_cnt[blockIdx.x] = sum;
-  }
+        if (stays) keep |= 1u << i;
+      });
+  tile_store_keep(keep, p0, s.nnz, keep_bits, tile_cnt, s_cnt);
 }
 
 static inline int64_t split_tasks(int64_t nnz) { return (nnz + kSplitTask - 1) / kSplitTask; }
@@ -630,20 +586,15 @@ int als_split_mark(const int64_t* row_ptr, const int32_t* col, int64_t nnz, int3
   hipStream_t st = as_stream(stream);
   const SplitSide s = split_side(row_ptr, col, nnz, n_rows, n_cols, row_ids, col_ids,
                                  rows_are_users, seed);
-  const int64_t tiles = remove_tiles(nnz);
+  const int64_t tiles = csr_tiles(nnz);
   int32_t* tile_cnt = static_cast<int32_t*>(scratch);
   if (tiles > 0) {
-    split_mark_kernel<<<(unsigned)tiles, kRemoveThreads, 0, st>>>(
+    split_mark_kernel<<<(unsigned)tiles, kTileThreads, 0, st>>>(
         s, selecting != 0, thr_lo_key, thr_lo_col, thr_hi_key, thr_hi_col, anchor, keep_bits,
         tile_cnt);
     ALS_LAUNCH_CHECK();
   }
-  remove_scan_kernel<<<1, kScanThreads, 0, st>>>(tile_cnt, tiles, tile_off);
-  ALS_LAUNCH_CHECK();
-  remove_row_ptr_kernel<<<(unsigned)(((int64_t)n_rows + 256) / 256), 256, 0, st>>>(
-      row_ptr, n_rows, nnz, keep_bits, tile_off, row_ptr_kept);
-  ALS_LAUNCH_CHECK();
-  return ALS_OK;
+  return keep_finish(row_ptr, n_rows, nnz, keep_bits, tile_cnt, tile_off, row_ptr_kept, st);
 }
 
 }  // extern "C"

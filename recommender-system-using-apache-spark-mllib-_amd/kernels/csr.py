@@ -147,6 +147,16 @@ def csr_remove_tile() -> int:
     return int(_lib.lib().als_csr_remove_tile())
 
 
+def keep_outputs(nnz: int, n_rows: int, dev):
+    """The three results of a mark call (als_csr_remove_mark, als_split_mark), unfilled:
+    (keep_bits int64 [ceil(nnz / 64)], tile_off int64 [tiles + 1], row_ptr_kept int64
+    [n_rows + 1])."""
+    tiles = -(-nnz // csr_remove_tile())
+    return (torch.empty(-(-nnz // 64), dtype=torch.int64, device=dev),
+            torch.empty(tiles + 1, dtype=torch.int64, device=dev),
+            torch.empty(n_rows + 1, dtype=torch.int64, device=dev))
+
+
 def remove_mark(row_ptr_old, col_old, row_ptr_del, col_del, ws: Workspace, count_hits=False):
     """K18, first call (als_csr_remove_mark): which stored entries of one side stay when the
     pairs of the delete CSR (row_ptr_del int64 [n + 1], col_del int32, every row's columns
@@ -159,10 +169,7 @@ def remove_mark(row_ptr_old, col_old, row_ptr_del, col_del, ws: Workspace, count
     dev = row_ptr_old.device
     n_old, nnz_old = int(row_ptr_old.numel()) - 1, int(col_old.numel())
     nnz_del = 0 if col_del is None else int(col_del.numel())
-    tiles = -(-nnz_old // csr_remove_tile())
-    keep_bits = torch.empty(-(-nnz_old // 64), dtype=torch.int64, device=dev)
-    tile_off = torch.empty(tiles + 1, dtype=torch.int64, device=dev)
-    row_ptr_kept = torch.empty(n_old + 1, dtype=torch.int64, device=dev)
+    keep_bits, tile_off, row_ptr_kept = keep_outputs(nnz_old, n_old, dev)
     hits = torch.empty(nnz_del, dtype=torch.int32, device=dev) if count_hits else None
     w = ws.get(L.als_csr_remove_scratch_bytes(nnz_old, n_old))
     check(L.als_csr_remove_mark(ptr(row_ptr_old), ptr(col_old), nnz_old, n_old, ptr(row_ptr_del),

@@ -7,7 +7,7 @@ import torch
 
 from .. import _lib
 from .._lib import check, ptr, stream_ptr
-from .csr import csr_remove_tile
+from .csr import keep_outputs
 from .workspace import Workspace
 
 SPLIT_MODES = ("count", "fraction", "fold")
@@ -81,10 +81,7 @@ def split_mark(row_ptr, col, n_cols: int, row_ids, col_ids, rows_are_users: bool
     format.  thr: split_thresholds' four arrays (of the selecting side)."""
     dev = row_ptr.device
     n_rows, nnz = int(row_ptr.numel()) - 1, int(col.numel())
-    tiles = -(-nnz // csr_remove_tile())
-    keep_bits = torch.empty(-(-nnz // 64), dtype=torch.int64, device=dev)
-    tile_off = torch.empty(tiles + 1, dtype=torch.int64, device=dev)
-    row_ptr_kept = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+    keep_bits, tile_off, row_ptr_kept = keep_outputs(nnz, n_rows, dev)
     w = _scratch(ws, nnz, n_rows)
     check(_lib.lib().als_split_mark(
         *_side_args(row_ptr, col, n_cols, row_ids, col_ids, rows_are_users, seed),

@@ -22,7 +22,7 @@ import numpy as np
 import split_ref as SR
 
 TASK = 2048          # kSplitTask of csrc/split.hip (test_csr_many_rows_cpu.py reads it there)
-BATCH = 256          # rows per trip of the row walk (kMergeThreads / kRemoveThreads)
+BATCH = 256          # rows per trip of the row walk (kTileThreads of csrc/csr_tile_walk.h)
 SCAN_TRIP = 4096     # tile counts per trip of remove_scan_kernel (kScanThreads * kScanItems)
 LONG_GRID = 2048     # kSplitLongGrid
 SEED = 20

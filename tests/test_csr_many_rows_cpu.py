@@ -36,11 +36,12 @@ def _max_empty_run(lens):
 # ---------------------------------------------------------------- constants
 def test_constants_are_the_sources():
     split, compact = GC._source("split.hip"), GC._source("csr_compact.h")
-    merge = GC._source("csr_merge.hip")
+    walk = GC._source("csr_tile_walk.h")   # the one geometry of the K17, K18 and K20 tiles
     assert GC.read_constant(split, "kSplitTask", "csrc/split.hip") == MR.TASK
     assert GC.read_constant(split, "kSplitLongGrid", "csrc/split.hip") == MR.LONG_GRID
-    assert GC.read_constant(merge, "kMergeThreads", "csrc/csr_merge.hip") == MR.BATCH
-    assert GC.read_constant(compact, "kRemoveThreads", "csrc/csr_compact.h") == MR.BATCH
+    assert GC.read_constant(walk, "kTileThreads", "csrc/csr_tile_walk.h") == MR.BATCH
+    for name in ("csr_merge.hip", "csr_remove.hip", "split.hip"):   # and no copy of it
+        assert "__launch_bounds__(kTileThreads)" in GC._source(name), name
     assert (GC.read_constant(compact, "kScanThreads", "csrc/csr_compact.h")
             * GC.read_constant(compact, "kScanItems", "csrc/csr_compact.h")) == MR.SCAN_TRIP
     T = _T()
